@@ -2,6 +2,8 @@
 """bench.py - fp64 Cholesky TFLOP/s on MI355X (BASELINE.json metric), one process per GPU.
 
     python bench.py --gpus 1 --steps 3 --warmup 1            # N = 65536 on one GPU
+    python bench.py --full                                    # ... plus the checks, rooflines, CPU baseline and extra_configs below
+    python bench.py --dump-outputs out                        # ... plus out/R.npy: a fixed sample of the last step's factor
     python bench.py --gpus 8 --steps 3 --warmup 1            # starts its own 8 ranks (one per GPU, RCCL) and relays rank 0's line
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
            --master-port 29501 bench.py --gpus 8 --steps 3 --warmup 1      # the same under an external launcher
@@ -14,7 +16,8 @@ barrier + sync, K calls, sync + barrier, max over ranks.
   cholesky: TFLOP/s := (N^3/3) / seconds-per-factor, N = 65536 for every GPU count ("strong" scaling).
   cacqr   : TFLOP/s := 4 m n^2 / seconds, m = 2^21 rows PER GPU ("weak" scaling), n = 256.
 
-The JSON line also carries
+A plain run sets up, warms up, times the steps, writes the last step's outputs if --dump-outputs DIR is given, and prints the
+JSON line (a non-zero `info` still fails it).  With --full the JSON line also carries
   config.residual - the reference validator's metric (test/cholesky/validate.hpp:33-46) of the LAST timed result,
                  computed after the timed region, plus an independent probe check (torch fp64 matmul);
                  a non-zero `info` or a residual above tolerance makes the run FAIL (value null, exit code 1),
@@ -86,11 +89,49 @@ def parse():
     ap.add_argument("--no-check", action="store_true", help="skip the residual checks (profiling runs)")
     ap.add_argument("--cpu-n", type=int, default=16384, help="bounded CPU-baseline sample size")
     ap.add_argument("--cpu-budget-s", type=float, default=100.0, help="seconds of host time the CPU baseline may take")
-    ap.add_argument("--check", action="store_true", help="(kept for compatibility: the residual is always computed)")
+    ap.add_argument("--check", action="store_true", help="(kept for compatibility: --full computes the residual)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: residual checks, rooflines, the CPU baseline and "
+                         "extra_configs (without it a run sets up, warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64; an output of more than "
+                         "%d entries as a fixed, seeded sample of them); one GPU" % DUMP_SAMPLE)
     args = ap.parse_args()
     if args.steps <= 0:
         args.steps = 20 if args.workload == "cacqr" else (5 if args.workload == "summa" else 3)      # a CholeskyQR2 step is 10 ms: average over more of them
+    if not args.full:
+        args.no_cpu_baseline = args.no_extra = args.no_check = True
+    if args.dump_outputs and (args.gpus != 1 or args.replay_rank is not None):
+        ap.error("--dump-outputs runs on one GPU, without --replay-rank")
     return args
+
+
+DUMP_SAMPLE = 1 << 21         # entries written of a larger output: 16 MB of float64, 4 outputs at most per workload
+
+
+def sample_positions(rows, cols, upper):
+    """The (row, col) positions --dump-outputs writes of a rows x cols output: all of them up to DUMP_SAMPLE entries, else
+    DUMP_SAMPLE positions drawn with a fixed seed (in the upper triangle for a triangular factor)."""
+    import numpy as np
+    if rows * cols <= DUMP_SAMPLE:
+        r, c = np.divmod(np.arange(rows * cols), cols)
+        return (r[r <= c], c[r <= c]) if upper else (r, c)
+    rng = np.random.default_rng(20261015)
+    r, c = rng.integers(0, rows, DUMP_SAMPLE), rng.integers(0, cols, DUMP_SAMPLE)
+    return (np.minimum(r, c), np.maximum(r, c)) if upper else (r, c)
+
+
+def dump_outputs(args, outputs):
+    """--dump-outputs: outputs = [(name, [row, col] device view, upper triangular?)] -> DIR/<name>.npy, float64, one value per
+    position of sample_positions (the whole output, row-major, when it is small enough)."""
+    if not args.dump_outputs:
+        return
+    import numpy as np
+    import torch
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, view, upper in outputs:
+        r, c = (torch.from_numpy(x).to(view.device) for x in sample_positions(view.shape[0], view.shape[1], upper))
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), view[r, c].to(torch.float64).cpu().numpy())
 
 
 def _largest_cube(limit):
@@ -524,6 +565,11 @@ def bench_cholesky(args, torch, L, C, rank, world, dist, emulate, timed, allredu
         A, pack, sec = single_gpu_case(n, args.complete_inv, args.steps, args.warmup)
         info = pack.last_info()
         parallelism = "1 GPU"
+        if args.dump_outputs:
+            outs = [("R", cholinv.construct_R(pack))] + ([("Rinv", cholinv.construct_Rinv(pack))] if args.complete_inv >= 0 else [])
+            dump_outputs(args, [(name, M.view(), True) for name, M in outs])
+            del outs
+            torch.cuda.empty_cache()
     else:
         ctx, sec, info, diag = multi_gpu_case(args, torch, L, C, rank, world, dist, emulate, allreduce_sum)
         parallelism = diag.pop("parallelism")
@@ -557,7 +603,7 @@ def bench_cholesky(args, torch, L, C, rank, world, dist, emulate, timed, allredu
         ok = ok and (res is None or (res == res and res <= RES_TOL)) and probe == probe and probe <= 1e-13
         torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and args.complete_inv < 0:
+    if args.full and rank == 0 and world == 1 and args.complete_inv < 0:
         # roofline of the dominant kernel, measured live (HIP events on its launch stream) on one more factor call
         pack.set_option("profile", 1)
         cholinv.factor(A, pack, None); torch.cuda.synchronize()
@@ -570,7 +616,7 @@ def bench_cholesky(args, torch, L, C, rank, world, dist, emulate, timed, allredu
                                "achieved": ach, "peak": FP64_MFMA_PEAK_TF, "unit": "TFLOP/s", "frac": ach / FP64_MFMA_PEAK_TF,
                                "launches": nl.value, "avg_launch_ms": ms.value / nl.value,
                                "algorithmic_flops_per_launch_avg": fl.value / nl.value, "traffic": traffic_from_profile(n, args)}
-    if world > 1 and sec is not None:
+    if args.full and world > 1 and sec is not None:
         r = ctx.roofline(L, C)
         if rank == 0 and r:
             out["roofline"] = r
@@ -618,7 +664,7 @@ def bench_cholesky(args, torch, L, C, rank, world, dist, emulate, timed, allredu
         # section 11: the mixed factorization 156 ms here against 134 ms alone) - the figure wanted is the workload's own.  In-process fallback
         # if the child cannot be run (or CAPITAL_BENCH_INPROC=1).
         def run_child(wl, steps):
-            cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", str(steps), "--warmup", "1", "--no-extra"]
+            cmd = [sys.executable, os.path.abspath(__file__), "--workload", wl, "--steps", str(steps), "--warmup", "1", "--full", "--no-extra"]
             if wl != "cacqr" or args.no_cpu_baseline:
                 cmd.append("--no-cpu-baseline")
             if args.no_check:
@@ -886,6 +932,7 @@ def bench_mixed(args, torch, L, C, rank, world, timed):
     sec = timed(step, args.steps, args.warmup)
     X, sweeps, relres = res["x"]
     info = p.last_info()
+    dump_outputs(args, [("X", X.view(), False)])
     tf_only = timed(lambda: p.factor(A), 2, 0)
     tflops = n ** 3 / 3.0 / sec / 1e12
     # check 1: ||A X - B||_F / ||B||_F recomputed with torch's fp64 matmul (rocBLAS), not this library's kernels.  A plain K = N
@@ -1039,6 +1086,7 @@ def bench_summa(args, torch, L, C, rank, world, timed):
             run = lambda: summa.invoke(A, Cm, T, pack)
             flops = 1.0 * N * (N + 1) * K
         sec = timed(run, steps, args.warmup)
+        dump_outputs(args, [("C_%s_%dx%dx%d" % (kind, M, N, K), Cm.view(), kind == "syrk")])
         tf = flops / sec / 1e12
         err = None
         if not args.no_check:
@@ -1097,6 +1145,10 @@ def bench_cacqr(args, torch, L, C, rank, world, dist, emulate, timed, allreduce_
     pack = cacqr.info(2, cholinv.info(1, 1, 0, 'U'))
     sec = timed(lambda: cacqr.factor(A, pack, topo), args.steps, args.warmup)
     info = pack.last_info()
+    if args.dump_outputs:
+        Q, R = cacqr.construct_Q(pack), cacqr.construct_R(pack)
+        dump_outputs(args, [("Q", Q.view(), False), ("R", R.view(), True)])
+        del Q, R
     flops = 4.0 * m * world * n * n
     abytes = 6.0 * 8 * m * n                                 # per GPU: 2 sweeps x (read A for the Gram + read A, write Q)
     tflops = flops / sec / 1e12

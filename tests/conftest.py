@@ -21,7 +21,9 @@ def golden_dir():
 
 def pytest_collection_finish(session):
     """Register the multi-rank GPU cases of the SELECTED tests so that tests/test_dist.py can run all cases of one rank count
-    inside one torch.distributed.run launch (see the comment there)."""
+    inside one torch.distributed.run launch (see the comment there); the launches too wide to share the GPU with this process run
+    here, before any test has opened it."""
+    mods = set()
     for item in session.items:
         spec = getattr(getattr(item, "function", None), "_dist_case", None)
         if spec is None or not hasattr(item, "callspec"):
@@ -30,3 +32,7 @@ def pytest_collection_finish(session):
         case = spec(**item.callspec.params)
         if case is not None and mod is not None:
             mod.register_case(*case)
+            mods.add(mod)
+    if not session.config.option.collectonly:
+        for mod in mods:
+            mod.run_wide_batches()

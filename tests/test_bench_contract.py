@@ -27,6 +27,13 @@ def test_defaults_match_the_baseline_metric():
     assert (a.gpus, a.n, a.complete_inv) == (1, 65536, -1)      # BASELINE.json: fp64 Cholesky, N = 65536
     assert a.steps >= 1 and a.warmup >= 1
     assert b.FP64_MFMA_PEAK_TF == 78.6
+    assert not a.full and a.no_check and a.no_extra and a.no_cpu_baseline and a.dump_outputs is None    # a plain run: the timed steps
+    sys.argv = ["bench.py", "--full", "--steps", "7"]
+    try:
+        a = b.parse()
+    finally:
+        sys.argv = old
+    assert a.full and not (a.no_check or a.no_extra or a.no_cpu_baseline) and a.steps == 7
 
 
 def test_cpu_baseline_leg_returns_a_reported_comparator():

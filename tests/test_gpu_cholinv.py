@@ -550,3 +550,26 @@ def test_profile_launch_by_launch_agrees_with_the_sums():
     _lib.check(L.cap_cholinv_profile_launches(pack._plan, msv, flv, 1, C.byref(cnt2)), "cap_cholinv_profile_launches")
     assert cnt2.value == cnt.value
     assert L.cap_cholinv_profile_launches(pack._plan, None, flv, cap, C.byref(cnt)) != 0       # argument check
+
+
+def test_bench_plain_run_dumps_the_factor_it_timed(tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: one JSON line with the headline fields, none of what --full adds, and DIR/R.npy
+    holds the factor of the last timed step at the positions bench.sample_positions names."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    n = 4096
+    r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), "--n", str(n),
+                        "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2 and d["dtype"] == "f64" and d["config"]["info"] == 0
+    assert not {"roofline", "cpu_baseline", "extra_configs"} & set(d) and "residual" not in d["config"]
+    got = np.load(str(tmp_path / "R.npy"))
+    rows, cols = bench.sample_positions(n, n, True)
+    assert got.dtype == np.float64 and got.shape == rows.shape
+    ref = np.linalg.cholesky(orc.symmetric_global(n, True)).T
+    assert relerr(got, ref[rows, cols]) < 1e-13

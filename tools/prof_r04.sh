@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; [ -z "$R" ] && R=$(pwd)
 OUT=$R/gpurun_out/prof_r04; rm -rf $OUT; mkdir -p $OUT/summary
 cd $R
-timeout 600 python bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err
+timeout 600 python bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err
 grep '^{' $OUT/bench_default.log > $OUT/summary/r04_bench_default_stdout.log; cut -c1-600 $OUT/summary/r04_bench_default_stdout.log
 cd /tmp
 timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/b65536 -o bench -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra > $OUT/b65536.log 2>&1
