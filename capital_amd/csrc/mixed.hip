@@ -521,14 +521,17 @@ int launch_bf16_head(int64_t m, int64_t n, int64_t k, float alpha, const __bf16*
 
 // Testing / benchmarking entry of the bf16 update (tests/test_gpu_mixed.py, tools/bf16_bench.py): C32[m x n] += alpha A^T B with A: k x m,
 // B: k x n bf16 (K-contiguous, lda / ldb elements), upper triangle only when tri.  variant 0 = round-3 kernel, 1 = second generation
-// (CAP_ERR_UNSUPPORTED where it does not apply), -1 = the dispatcher the factorization uses.  tpw > 0 overrides the chunk length.
+// (CAP_ERR_UNSUPPORTED where it does not apply), -1 = the dispatcher the factorization uses.  tpw > 0 overrides the chunk length (the
+// supertile edge for variants 3 - 6) of this call only.
 extern "C" int cap_bf16_update(int variant, int64_t m, int64_t n, int64_t k, float alpha, const void* A16, int64_t lda, const void* B16, int64_t ldb,
                                float* C, int64_t ldc, int tri, int tpw, void* stream) {
   if (!A16 || !B16 || !C || m < 0 || n < 0 || k < 0) return CAP_ERR_ARG;
-  if (tpw > 0 && (variant < 3 || (variant > 6 && variant < 300))) g_bf16_tpw = tpw;
+  // tpw applies to this call only (like the schedule switches below): the factorization keeps the process-wide chunk length
+  const int tpw_saved = g_bf16_tpw;
+  if (tpw > 0 && variant < 0) g_bf16_tpw = tpw;
   const __bf16* A = (const __bf16*)A16; const __bf16* B = (const __bf16*)B16;
   hipStream_t s = cap_stream(stream);
-  if (variant < 0) return launch_bf16_update(m, n, k, alpha, A, lda, B, ldb, C, ldc, tri, s);
+  if (variant < 0) { const int st = launch_bf16_update(m, n, k, alpha, A, lda, B, ldb, C, ldc, tri, s); g_bf16_tpw = tpw_saved; return st; }
   if (variant == 0) return launch_bf16_tn(m, n, k, alpha, A, lda, B, ldb, C, ldc, tri, s);
   if (variant >= 3 && variant <= 6)      // third generation (6: wide staging with 32-MFMA phases): LDS ring of 3 / 4 stages of 32 k, 5 = two stages of 64 k; tpw carries the supertile edge here (0: default)
     return cap_bf16_tn3_launch(m, n, k, alpha, A, lda, B, ldb, C, ldc, tri, variant, tpw > 0 ? tpw : g_bf16_v3_st, s);
@@ -542,9 +545,9 @@ extern "C" int cap_bf16_update(int variant, int64_t m, int64_t n, int64_t k, flo
   // variant 1: the production schedule; 2: without the forced read-ahead; 100 + DBG: timing surgery (experiment builds only)
   g_bf16_sched = variant == 2 ? 0 : 1;
   g_bf16_dbg = variant >= 100 ? variant - 100 : 0;
-  if (g_bf16_dbg && !CAP_EXPERIMENTS) return CAP_ERR_UNSUPPORTED;
-  const int st = launch_bf16_v2(m, n, k, alpha, A, lda, B, ldb, C, ldc, tri, s);
-  g_bf16_sched = 1; g_bf16_dbg = 0;
+  if (tpw > 0) g_bf16_tpw = tpw;
+  const int st = (g_bf16_dbg && !CAP_EXPERIMENTS) ? (int)CAP_ERR_UNSUPPORTED : launch_bf16_v2(m, n, k, alpha, A, lda, B, ldb, C, ldc, tri, s);
+  g_bf16_sched = 1; g_bf16_dbg = 0; g_bf16_tpw = tpw_saved;
   return st;
 }
 

@@ -656,8 +656,20 @@ void k_scatter_rows_bc(void** a, unsigned gy) {
   for (int64_t c = 0; c < std::min<int64_t>(cols, gy); c++) for (int64_t l = 0; l < lc; l++) Out[((l / nb) * P + p) * nb + l % nb + c * ldo] = Q[l + c * ldq];
 }
 // bf16_tn_kernel: C (fp32) += alpha A^T B on 128 x 128 tiles, the launch's blocks walked as the kernel walks them
+// SHIM_FAULT="kind:n" of the bf16 family (next to kinds 1 - 4 of the fp64 one): the n-th launch of a bf16 update kernel runs with ONE thing
+// wrong - 5: the tile grid is one tile column short, 6: K is one K stage short
+static long bf16_fault_seen = 0;
 void k_bf16_tn(void** a, unsigned gx, const int TB = 128, const int KG = 64) {
-  const BfArgs g = arg<BfArgs>(a, 0);
+  BfArgs g = arg<BfArgs>(a, 0);
+  static const char* fault = getenv("SHIM_FAULT");
+  if (fault) {
+    const int kind = atoi(fault); const char* c = strchr(fault, ':'); const long nth = c ? atol(c + 1) : 0;
+    const bool applies = (kind == 5 && g.tn > 1 && !g.stair) || (kind == 6 && g.K > KG);
+    if (applies && bf16_fault_seen++ == nth) {
+      if (kind == 5) g.tn -= 1;
+      if (kind == 6) g.K -= KG;
+    }
+  }
   const bf16_t* A = reinterpret_cast<const bf16_t*>(g.A); const bf16_t* B = reinterpret_cast<const bf16_t*>(g.B);
   struct Tile { int ti, tj, gtj; const bf16_t* Abase; };
   std::vector<Tile> tiles;

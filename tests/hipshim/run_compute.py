@@ -669,6 +669,13 @@ def mixed_compute(r, errors, n, nrhs, opts=(), seed=4, reps=1):
     e32 = rel(np.triu(r32.astype(np.float64)), np.linalg.cholesky(a).T)
     errors["info"] = float(abs(info.value))
     errors["factor is a bf16-update factor (1e-6 < err < 5e-2)"] = 0.0 if 1e-6 < e32 < 5e-2 else e32 + 1.0
+    # element by element: the rounding model (tests/mixed_model.py) replayed on the factor's own bf16 panels, normwise and per 256 x 256
+    # tile; scaled so that the gate (TOL) sits at the model's tolerances
+    from tests import mixed_model as mm
+    r32u = np.triu(r32.astype(np.float64))
+    rep = mm.factor(a, solve3=bool(dict(opts).get("solve3", 1)), panels_of=r32u)
+    tn, tt = mm.tolerances(n)
+    errors["R32 vs rounding model (scaled)"] = max(rel(r32u, rep) / tn, float(mm.tile_errors(r32u, rep).max()) / tt) * TOL
     errors["sweeps within 1..25"] = 0.0 if 1 <= it.value <= 25 else float(it.value) + 1.0
     errors["B - A X (scaled to the tolerance)"] = float(np.linalg.norm(a @ x - b) / np.linalg.norm(b)) * 1e-3      # <= 2e-14 passes the 2e-11 gate
     errors["X vs fp64 solve (scaled)"] = rel(x, np.linalg.solve(a, b)) * 1e-2

@@ -183,3 +183,33 @@ def test_the_plain_c_drivers_run_on_the_cpu(tmp_path, name, argv, checks):
         m = re.search(r"\b%s\b[^=\n]*?=?\s*([0-9.]+e[+-][0-9]+)" % word, run.stdout)
         assert m, (word, run.stdout[-1500:])
         assert float(m.group(1)) <= bound, (word, m.group(1), run.stdout[-1500:])
+
+
+@pytest.mark.parametrize("fault,what", [("5:2", "a bf16 update whose tile grid is one tile column short"), ("6:2", "a bf16 update whose K is one K stage short")])
+def test_one_wrong_bf16_launch_is_noticed_by_the_rounding_model(fault, what):
+    """teeth of the "R32 vs rounding model" entry (tests/mixed_model.py): the mixed factorization of N = 3072 with ONE bf16 update
+    kernel launch handed over wrong (SHIM_FAULT kinds 5, 6) fails it; unfaulted it passes.  The bf16-band window kept beside it
+    (1e-6 < err < 5e-2) does not notice either fault: the factor stays a usable bf16-class factor and refinement still converges."""
+    code = r"""
+import sys
+sys.path.insert(0, %r)
+import run_compute as rc
+rc.shim.shim_set_compute(1)
+e = {}
+r = rc.rs.Run("fault", 0)
+rc.mixed_compute(r, e, 3072, 4)
+print("M %%.3e W %%.3e" %% (e["R32 vs rounding model (scaled)"], e["factor is a bf16-update factor (1e-6 < err < 5e-2)"]))
+""" % os.path.join(ROOT, "tests", "hipshim")
+    env = dict(os.environ); env.pop("LD_PRELOAD", None); env["SHIM_FILTER"] = ""; env["SHIM_KEEP_TRACE"] = ""
+    out = {}
+    for f in ("", fault):
+        env["SHIM_FAULT"] = f
+        if not f:
+            env.pop("SHIM_FAULT")
+        r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        w = r.stdout.strip().splitlines()[-1].split()
+        out[f] = (float(w[1]), float(w[3]))
+    assert out[""][0] < 2e-11 and out[""][1] == 0.0, out
+    assert out[fault][0] > 10 * 2e-11 or out[fault][0] != out[fault][0], (what, out)
+    assert out[fault][1] == 0.0, (what, out)          # (the old window alone would have passed it)

@@ -6,7 +6,27 @@ import torch
 pytestmark = pytest.mark.gpu
 
 from oracle import capital_oracle as orc  # noqa: E402
+from tests import mixed_model as mm  # noqa: E402
 from tests.gpu_util import relerr  # noqa: E402
+
+# the process-wide selector of the bf16 update (cap_mpchol_set_option: update_kernel, update_min_tiles, update_v3_*, update_tpw) as
+# shipped (csrc/mixed.hip); every test of this module leaves it so, whatever it switched
+SELECTOR_DEFAULTS = (("update_kernel", 6), ("update_min_tiles", 1024), ("update_v3_min_tiles", 64), ("update_v3_head_min_tiles", 32),
+                     ("update_v3_st", 4), ("update_tpw", 8))
+
+
+def _restore_selector():
+    from capital_amd import mixed
+    p = mixed.plan(128, 1)
+    for k, v in SELECTOR_DEFAULTS:
+        p.set_option(k, v)
+    p.close()
+
+
+@pytest.fixture(autouse=True)
+def _selector_restored():
+    yield
+    _restore_selector()
 
 
 def _spd(n, kind, seed=0):
@@ -266,8 +286,200 @@ def test_bf16_update_dispatcher_and_refusals():
         p.factor(A)
         assert p.last_info() == 0
         fs.append(p.R32().cpu().numpy().astype(np.float64))
-        p.set_option("update_kernel", 0); p.set_option("update_min_tiles", 1024)
         p.close()
+    _restore_selector()
+    p = mixed.plan(n, 4)                          # the shipped kernel (6) with the shipped thresholds
+    p.factor(A)
+    assert p.last_info() == 0
+    fs.append(p.R32().cpu().numpy().astype(np.float64))
+    p.close()
     ref = np.linalg.cholesky(a).T
-    assert relerr(fs[0], ref) < 2e-2 and relerr(fs[1], ref) < 2e-2
+    assert relerr(fs[0], ref) < 2e-2 and relerr(fs[1], ref) < 2e-2 and relerr(fs[2], ref) < 2e-2
     assert relerr(fs[1], fs[0]) < 1e-3            # same bf16 panels up to rare rounding flips; fp32 sums in a different order
+    assert relerr(fs[2], fs[0]) < 1e-3
+    # the kernels 0 and 6 sum every element in the same k order with one final add: the whole factorization agrees bit for bit
+    assert np.array_equal(fs[2], fs[0])
+
+
+# ---- the factor element by element: against the rounding model (tests/mixed_model.py) --------------------------------------------
+_INPUTS = {}
+
+
+def _input(n, kind):
+    """(fp64 host matrix, device matrix) per (n, kind), built once per module"""
+    from capital_amd.matrix import matrix
+    if (n, kind) not in _INPUTS:
+        a = _spd(n, kind, seed=n)
+        _INPUTS[(n, kind)] = (a, matrix(n, n, 1, 1).from_numpy(a))
+    return _INPUTS[(n, kind)]
+
+
+def _dev_matmul(x, y):
+    """the model's fp64 products on the device (the same sums to fp64 rounding; host BLAS took 7 s per model at n = 9216)"""
+    return (torch.from_numpy(np.ascontiguousarray(x)).cuda() @ torch.from_numpy(np.ascontiguousarray(y)).cuda()).cpu().numpy()
+
+
+# (at 9216 a case costs ~ 8 s of host work, input and model: the diagonally dominant input (kappa ~ 1, the least demanding) and the
+# options other than pair_rest, which needs >= 8 panels, run at the smaller sizes only)
+_MODEL_CASES = ([(n, kind, ()) for n in (640, 896, 2048, 3072, 5248, 9216) for kind in ("reference", "gram", "spd") if (n, kind) != (9216, "reference")] +
+                [(n, kind, opts) for (n, kind) in ((3072, "spd"), (5248, "gram")) for opts in
+                 ((("strip", 1),), (("split", 0),), (("solve3", 0),), (("pair_rest", 0),))] +
+                [(9216, "spd", (("pair_rest", 0),)), (6144, "gram", (("update_kernel", 1), ("update_min_tiles", 0)))])
+
+
+@pytest.mark.parametrize("n,kind,opts", _MODEL_CASES)
+def test_factor_against_the_rounding_model(n, kind, opts):
+    """R32 against the rounding model replayed on R32's own bf16 panels (mixed_model.factor(panels_of=)): every diagonal block, block row
+    and trailing-update tile of the factor is what the documented arithmetic makes of the history the factor really had, to fp32-sum
+    level - normwise and per 256 x 256 tile (a defect confined to one tile cannot hide in the global norm).  Sizes: nb < 1024 (640, 896),
+    one / two / three panels, a ragged last panel (5248), the paired far update (9216), kernel 1 (its fp32 sums in another order).
+    (The model run on its own panels instead drifts from the factor by bf16 ulps: one element rounded to the other side of a bf16
+    boundary changes every update behind it, and the flips cascade - up to 4e-4 normwise at n = 5248, kappa ~ 200, as much as a
+    truncating conversion.  Replaying keeps the comparison at the fp32 level: tests/mixed_model.py, tolerances.)"""
+    from capital_amd import mixed
+    a, A = _input(n, kind)
+    p = mixed.plan(n, 4)
+    for k, v in opts:
+        p.set_option(k, v)
+    p.factor(A)
+    assert p.last_info() == 0
+    r32 = p.R32().cpu().numpy().astype(np.float64)
+    p.close()
+    assert np.array_equal(np.tril(r32, -1), np.zeros_like(r32))
+    rep = mm.factor(a, solve3=bool(dict(opts).get("solve3", 1)), panels_of=r32, matmul=_dev_matmul)
+    tn, tt = mm.tolerances(n)
+    norm, tiles = relerr(r32, rep), mm.tile_errors(r32, rep)
+    worst = np.unravel_index(np.argmax(tiles), tiles.shape)
+    print("MODEL n=%d %s %s norm %.3e tile %.3e at %s (tol %.1e / %.1e)" % (n, kind, dict(opts), norm, tiles.max(), worst, tn, tt))
+    assert norm < tn and tiles.max() < tt, (norm, tiles.max(), worst, tn, tt)
+    assert relerr(r32, np.linalg.cholesky(a).T) < 2e-2
+
+
+# ---- the update-kernel selector: every kernel choice gives the same bits ----------------------------------------------------------
+_SELECTOR_CASES = (("default", ()), ("kernel 0", (("update_kernel", 0),)), ("kernel 3", (("update_kernel", 3),)), ("kernel 4", (("update_kernel", 4),)),
+                   ("kernel 5", (("update_kernel", 5),)),
+                   ("kernel 6 on every launch", (("update_v3_min_tiles", 0), ("update_v3_head_min_tiles", 0))),
+                   ("no kernel 6 on the panel stream", (("update_v3_head_min_tiles", -1),)),
+                   ("supertile edge 1", (("update_v3_st", 1),)), ("supertile edge 8", (("update_v3_st", 8),)))
+
+
+@pytest.mark.parametrize("n", [5248, 9216])
+def test_update_kernel_choice_does_not_change_a_bit(n):
+    """Kernels 0 and 3 - 6 sum every element of a launch in the same k order and add it into C once (bit for bit per launch:
+    test_bf16_update_third_generation), and every C element receives its launches in a fixed order.  So R32 and the refined X are
+    bit-identical whichever of them the selector picks, wherever it picks it: the default; 0, 3, 4, 5 on every big update; kernel 6 on
+    every launch of every stream (update_v3_min_tiles = head_min = 0: the non-atomic read-add-store epilogue everywhere - one writer per
+    C element and launch); none on the panel stream; supertile edges 1 and 8.  (Kernel 1 sums in another order: against the model above.)"""
+    from capital_amd import _lib, mixed
+    from capital_amd.matrix import matrix
+    a, A = _input(n, "gram")
+    b = np.random.default_rng(5).standard_normal((n, 4)); B = matrix(4, n, 1, 1).from_numpy(b)
+    ref = None
+    for name, opts in _SELECTOR_CASES:
+        _restore_selector()
+        p = mixed.plan(n, 4)
+        for k, v in opts:
+            p.set_option(k, v)
+        p.factor(A)
+        assert p.last_info() == 0, name
+        r32 = p.R32().clone()
+        X, iters, rr = p.solve(A, B)
+        x = X.to_numpy()
+        p.close()
+        assert rr <= 1e-14, (name, rr, iters)
+        if ref is None:
+            ref = (r32, x)
+            continue
+        assert torch.equal(r32, ref[0]), (name, float((r32.double() - ref[0].double()).abs().max()))
+        assert np.array_equal(x, ref[1]), name
+
+
+# ---- substitution and one refinement sweep against host fp64 ----------------------------------------------------------------------
+@pytest.mark.parametrize("nrhs", [1, 8, 9, 130])
+def test_substitution_and_one_sweep_against_host_fp64(nrhs):
+    """max_iter = 0 returns the plain substitution x0 = R^-1 R^-T b, max_iter = 1 one refinement sweep; both against scipy's
+    solve_triangular on fp64(R32) (nrhs <= 8: the skinny kernels streaming the fp32 factor; above: the 128-wide tile path).
+    The device's diagonal-block inverses come from the unrounded fp64 R_kk, the off-diagonal blocks from fp64(R32): it solves with a
+    factor R' whose diagonal blocks differ from fp64(R32) by one fp32 rounding, |R' - R| <= 2^-24 |R| elementwise.  Each triangular
+    solve then moves x by at most kappa(R) ||R' - R|| / ||R|| <= kappa(R) 2^-24 (first order), two solves 2 kappa(R) 2^-24;
+    bound: 4 kappa(R) 2^-24 sqrt(2) (normwise of an elementwise bound, margin 2).  A wrong block step is off by 1e-3 or more."""
+    from scipy.linalg import solve_triangular
+    from capital_amd import mixed
+    from capital_amd.matrix import matrix
+    n = 3072
+    a, A = _input(n, "spd")
+    b = np.random.default_rng(nrhs).standard_normal((n, nrhs))
+    B = matrix(nrhs, n, 1, 1).from_numpy(b)
+    p = mixed.plan(n, 130)
+    p.factor(A)
+    assert p.last_info() == 0
+    r64 = p.R32().cpu().numpy().astype(np.float64)
+    X0, it0, rr0 = p.solve(A, B, max_iter=0)
+    X1, it1, rr1 = p.solve(A, B, max_iter=1)
+    p.close()
+    x0, x1 = X0.to_numpy(), X1.to_numpy()
+    assert it0 == 0 and it1 == 1
+    ev = torch.linalg.eigvalsh(torch.from_numpy(a).cuda()).cpu().numpy()      # kappa(R) = sqrt(kappa(A)) (R' ~ R within 1e-3)
+    kr = float(np.sqrt(ev[-1] / ev[0]))
+    tol = 4 * kr * 2.0 ** -24 * 2 ** 0.5
+    h0 = solve_triangular(r64, solve_triangular(r64, b, trans="T"))
+    e0 = relerr(x0, h0)
+    res0 = b - a @ x0
+    hrr0 = np.linalg.norm(res0) / np.linalg.norm(b)
+    # one sweep: x1 = x0 + R'^-1 R'^-T (b - A x0); the correction carries the same relative error as x0 did
+    d = solve_triangular(r64, solve_triangular(r64, res0, trans="T"))
+    h1 = x0 + d
+    e1 = np.linalg.norm(x1 - h1) / np.linalg.norm(d)
+    hrr1 = np.linalg.norm(b - a @ x1) / np.linalg.norm(b)
+    print("SUBST nrhs=%d kappa(R) %.1f x0 %.3e sweep %.3e (tol %.1e) relres %.3e / %.3e, %.3e / %.3e" % (nrhs, kr, e0, e1, tol, rr0, hrr0, rr1, hrr1))
+    assert e0 < tol and e1 < tol, (e0, e1, tol)
+    assert abs(rr0 - hrr0) <= 1e-8 * hrr0 and abs(rr1 - hrr1) <= 1e-6 * hrr1 + 1e-15, (rr0, hrr0, rr1, hrr1)
+    assert hrr1 < 0.1 * hrr0                                      # the sweep refined
+
+
+# ---- the bf16 update at the bench geometry ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("K", [2048, 4096])
+def test_bf16_update_at_the_bench_geometry(K):
+    """m = n = 65536, ldc = 65568 (17 GB of fp32 C: tiles more than 2^32 bytes from the base, per-tile 64-bit bases and 32-bit buffer
+    offsets, bf16_tn3.hip) and a 2048-row strip of it (m < n), every kernel: sampled tiles - the first and last diagonal tiles, the far
+    corner, random upper tiles - against torch fp64 of the same bf16 operands, bit for bit across the kernels 0 / 3 - 6, sampled
+    strictly-lower tiles and the padding rows [m, ldc) untouched.  C is regenerated from a fixed seed before each kernel."""
+    N, ldc, T = 65536, 65568, 256
+    g = torch.Generator(device="cuda"); g.manual_seed(K)
+    a16 = torch.randn(N, K, device="cuda", generator=g).to(torch.bfloat16)
+    c = torch.empty(N, ldc, device="cuda")                       # C^T: [col, row]
+    rng = np.random.default_rng(K)
+    up = [(0, 0), (N // T - 1, N // T - 1), (0, N // T - 1), (N // T - 2, N // T - 1)] + \
+         [tuple(sorted(rng.integers(0, N // T, 2))) for _ in range(8)]
+    low = [(N // T - 1, 0), (N // T - 1, N // T - 2)] + [tuple(sorted(rng.integers(0, N // T, 2), reverse=True)) for _ in range(4)]
+    low = [(i, j) for (i, j) in low if i > j]
+    tol = 4e-6 * (K / 64.0) ** 0.5
+    for m, tiles in ((N, up), (2048, [(0, 0), (7, 7), (0, N // T - 1), (7, N // T - 1), (3, 100)])):
+        lows = [t for t in low if t[0] * T < m] + ([(7, 0), (7, 6)] if m < N else [])
+        got = {}
+        for variant in (-1, 0, 1, 3, 4, 5, 6):
+            gc = torch.Generator(device="cuda"); gc.manual_seed(17)
+            torch.randn(N, ldc, device="cuda", generator=gc, out=c)
+            before = {t: c[t[1] * T:(t[1] + 1) * T, t[0] * T:(t[0] + 1) * T].clone() for t in tiles + lows}
+            pad = c[:, m:].clone() if m == N else c[:, m:m + 64].clone()
+            st = _bf16_update(variant, a16[:m], a16, c, -1.0, 1)
+            if variant == 1 and m != N:
+                assert st != 0                                     # the second generation refuses strips of a triangular update
+                continue
+            assert st == 0, (variant, st)
+            torch.cuda.synchronize()
+            for (i, j) in tiles:
+                blk = c[j * T:(j + 1) * T, i * T:(i + 1) * T].t()
+                ref = before[(i, j)].t().double() - a16[i * T:(i + 1) * T].double() @ a16[j * T:(j + 1) * T].double().t()
+                mask = torch.triu(torch.ones(T, T, dtype=torch.bool, device="cuda")) if i == j else torch.ones(T, T, dtype=torch.bool, device="cuda")
+                err = float((blk.double() - ref)[mask].abs().max()) / float(ref.abs().max())
+                assert err < tol, (m, variant, (i, j), err, tol)
+                if i == j:
+                    assert torch.equal(blk[~mask], before[(i, j)].t()[~mask]), (m, variant, (i, j))
+                got.setdefault((i, j), {})[variant] = blk.clone()
+            for t in lows:
+                assert torch.equal(c[t[1] * T:(t[1] + 1) * T, t[0] * T:(t[0] + 1) * T], before[t]), (m, variant, t)
+            assert torch.equal(c[:, m:] if m == N else c[:, m:m + 64], pad), (m, variant)
+        for t, outs in got.items():
+            for v in (3, 4, 5, 6):
+                assert torch.equal(outs[v], outs[0]), (m, t, v)
