@@ -29,6 +29,8 @@ SIGNATURES = {
     "cap_dtrsm_work_size": (i64, [cint, i64, i64]),
     "cap_dpotrf": (cint, [cint, i64, ptr, i64, ptr, ptr, ptr]),
     "cap_dpotrf_work_size": (i64, [i64]),
+    "cap_dpotrs": (cint, [cint, i64, i64, ptr, i64, ptr, i64, ptr, ptr]),
+    "cap_dpotrs_work_size": (i64, [i64, i64]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_desc_create": (cint, [C.POINTER(ptr), i64, i64, i64, i64]),
@@ -94,6 +96,7 @@ SIGNATURES = {
     "cap_cholinv_get_Rinv": (cint, [ptr, ptr, i64, ptr]),
     "cap_cholinv_R_ptr": (ptr, [ptr, C.POINTER(i64)]),
     "cap_cholinv_Rinv_ptr": (ptr, [ptr, C.POINTER(i64)]),
+    "cap_cholinv_solve": (cint, [ptr, ptr, i64, ptr, i64, i64, ptr]),
     "cap_cholinv_info": (cint, [ptr, ptr, C.POINTER(i64)]),
     "cap_cholinv_set_option": (cint, [ptr, C.c_char_p, i64]),
     "cap_cholinv_get_option": (i64, [ptr, C.c_char_p]),
@@ -149,6 +152,8 @@ SIGNATURES = {
     "cap_mpchol_profile": (cint, [ptr, C.POINTER(i64), C.POINTER(dbl), C.POINTER(dbl), C.POINTER(dbl)]),
     "cap_chain_fallbacks": (i64, []),
     "cap_chain_inject_timeouts": (cint, [cint]),
+    "cap_solve_fallbacks": (i64, []),
+    "cap_solve_inject_timeouts": (cint, [cint]),
     "cap_bf16_update": (cint, [cint, i64, i64, i64, C.c_float, ptr, i64, ptr, i64, ptr, i64, cint, cint, ptr]),
     "cap_dmp_plan_create": (cint, [C.POINTER(ptr), i64, i64, i64, ptr]),
     "cap_dmp_plan_destroy": (cint, [ptr]),

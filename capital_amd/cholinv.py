@@ -3,6 +3,7 @@
     pack = cholinv.info(complete_inv, split, bc_mult_dim, 'U')     # plan handle (create once)
     cholinv.factor(A, pack, topo)                                   # A: matrix (read-only)
     R = cholinv.construct_R(pack, topo); Rinv = cholinv.construct_Rinv(pack, topo)
+    X = cholinv.solve(B, pack)                                      # A X = B with the factor of the last factor call
 
 `info` keeps upstream's four user knobs.  complete_inv = -1 is the documented extension:
 blocked right-looking Cholesky (real TRSM/SYRK, no explicit inverse) - the headline
@@ -117,3 +118,21 @@ def construct_R(args, CommInfo=None):
 def construct_Rinv(args, CommInfo=None):
     """cholinv.hpp:39-46."""
     return _construct(args, "Rinv")
+
+
+def solve(B, args, X=None):
+    """A X = B with the factor `cholinv.factor` left in `args` (single-GPU plans; the reference's trsm::diaginvert is a stub).
+    B: n x nrhs matrix (not written unless X is B); X: a matrix of the same shape, or None for a new one.  Asynchronous on the
+    current stream.  A failing pivot of the last factor call leaves X NaN (args.last_info() reports it)."""
+    if args._plan is None:
+        raise _lib.CapitalError("cholinv.solve needs a plan that cholinv.factor has filled")
+    n, nrhs = B.num_rows_global(), B.num_columns_global()
+    if n != args._n:
+        raise _lib.CapitalError("B has %d rows, the factor is %d x %d" % (n, args._n, args._n))
+    if X is None:
+        X = matrix(nrhs, n, 1, 1, rect)
+    elif X.num_rows_global() != n or X.num_columns_global() != nrhs:
+        raise _lib.CapitalError("X must be %d x %d" % (n, nrhs))
+    _lib.check(_lib.lib().cap_cholinv_solve(args._plan, B.data_ptr(), B.ld(), X.data_ptr(), X.ld(), nrhs, cur_stream()),
+               "cholinv::solve")
+    return X

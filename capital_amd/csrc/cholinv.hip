@@ -395,6 +395,11 @@ struct cap_cholinv_plan {
   InvTree* itree; bool inv_active; int inv_tree_skip; int64_t inv_tree_mid;
   double* inv_W;        // tree scratch (inside `work`)
   hipStream_t s_inv; std::vector<hipEvent_t>* ev_pf; hipEvent_t ev_inv_done; bool inv_ready; int inv_pending_from;
+  // solve (cap_cholinv_solve): every factor call starts a new generation; the inverses of R's diagonal blocks are made by the first solve
+  // after it (block width sv_inv_tb) and kept for the later ones.  sv_work: the solve's scratch.  Both are allocated on first use.
+  int64_t gen; int solve_kernel;
+  double* sv_inv; int64_t sv_inv_elems, sv_inv_tb, sv_inv_gen;
+  double* sv_work; int64_t sv_work_elems;
 };
 
 namespace {
@@ -1136,6 +1141,7 @@ int cap_cholinv_plan_create(cap_cholinv_plan** plan, int64_t n, int complete_inv
   p->inv_fast = CAP_ENV("CAP_INV_FAST") ? atoi(CAP_ENV("CAP_INV_FAST")) : 1;
   p->inv_overlap = CAP_ENV("CAP_INV_OVERLAP") ? atoi(CAP_ENV("CAP_INV_OVERLAP")) : 1;
   p->inv_start_m = CAP_ENV("CAP_INV_START_M") ? atoll(CAP_ENV("CAP_INV_START_M")) : std::max<int64_t>(16384, n / 2);
+  p->solve_kernel = 1;
   int st = plan_alloc(p);
   if (st != CAP_OK) { cap_cholinv_plan_destroy(p); return st; }
   *plan = p;
@@ -1152,6 +1158,8 @@ int cap_cholinv_plan_destroy(cap_cholinv_plan* p) {
   if (p->Rinv) (void)hipFree(p->Rinv);
   if (p->work) (void)hipFree(p->work);
   if (p->info_dev) (void)hipFree(p->info_dev);
+  if (p->sv_inv) (void)hipFree(p->sv_inv);
+  if (p->sv_work) (void)hipFree(p->sv_work);
   if (p->streams_ready) {
     cap_stream_destroy(p->s_panel);
     for (int i = 0; i < 2; i++) { (void)hipEventDestroy(p->ev_panel[i]); (void)hipEventDestroy(p->ev_update[i]); }
@@ -1176,6 +1184,8 @@ int cap_cholinv_set_option(cap_cholinv_plan* p, const char* key, int64_t value) 
   // resident workgroups of the one-launch diagonal-block chain (leaf.hip chain64_coop_kernel) for THIS plan's factor calls (also a
   // multi-rank plan's: the schedule behind it runs on the calling thread), 0 = one launch per step; -1 = back to the process default
   if (k == "chain_coop") { if (value < -1 || value > 256) return CAP_ERR_ARG; p->chain_coop = (int)value; return CAP_OK; }
+  // nrhs <= 16 solves: 1 = the one-launch substitutions of potrs.hip (default), 0 = the blocked substitution of cap_dtrsm
+  if (k == "solve_kernel") { if (value < 0 || value > 1) return CAP_ERR_ARG; p->solve_kernel = (int)value; return CAP_OK; }
   if (p->dist) {
     if (k == "nb") {        // block width of the distribution: rebuild the inner plan
       if (value < 128 || value % 128) return CAP_ERR_ARG;
@@ -1254,6 +1264,7 @@ int64_t cap_cholinv_get_option(cap_cholinv_plan* p, const char* key) {
   std::string k(key);
   if (k == "chain_coop") { if (p->chain_coop >= 0) return p->chain_coop; return cap_chain_coop_get(); }
   if (k == "chain_fallbacks") return cap_chain_fallbacks();
+  if (k == "solve_kernel") return p->solve_kernel;
   if (p->dist) {
     if (k == "complete_inv") return p->complete_inv;
     if (k == "split") return p->split;
@@ -1301,6 +1312,7 @@ int cap_cholinv_factor(cap_cholinv_plan* p, const double* A, int64_t lda, void* 
   if (!A || lda < p->n) return CAP_ERR_ARG;
   hipStream_t s = cap_stream(stream);
   const int64_t n = p->n;
+  p->gen++;                                  // the solve's cached block inverses belong to the previous factor
   CAP_HIP(hipMemsetAsync(p->info_dev, 0, sizeof(int), s));
   // serialize<uppertri,uppertri>(A -> R), cholinv.hpp:13: only A's upper triangle is consumed
   p->srcA = A; p->src_lda = lda;             // right_looking does the A -> R copy (all of it, or the first strip's rows)
@@ -1486,6 +1498,83 @@ int cap_dtrtri(int uplo, int64_t n, double* A, int64_t lda, double* work, void* 
   CAP_TRY(cap_copy_window(A, 0, lda, 0, 0, T, 0, n, 0, 0, n, n, 1, 1, stream));
   CAP_TRY(rec_trtri(T, n, n, W, rec_work_size(n), CAP_LEAF_MAX, s));
   return cap_copy_window(T, 0, n, 0, 0, A, 0, lda, 0, 0, n, n, 1, 0, stream);
+}
+
+// ---- POTRS: A X = B with A = R^T R, as two substitutions R^T Y = B, R X = Y over the inverses of R's diagonal blocks (the design of the
+// reference's trsm::diaginvert stub, src/alg/trsm/diaginvert/diaginvert.hpp:7-10).  nrhs <= 16 (and "solve_kernel" = 1): one launch
+// per substitution (potrs.hip, block width 128), each with its recovery launch behind it; the forward one writes Y into scratch, so the
+// caller's B is only read, and the backward one writes X.  More right-hand sides: the blocked substitution of cap_dtrsm (an MFMA GEMM
+// per block step, compute-bound there) on X.  `info` != 0 after the factor: X is NaN.
+// scratch of the one-launch path: [counter words of both launches][Y][S], each vector ldy = nb 128 rows
+static int64_t potrs_ldy(int64_t n) { return cap_round_up(n, cap_potrs_block()); }
+static int64_t potrs_scratch_elems(int64_t n, int64_t nrhs, bool one, int64_t tb) {
+  if (!one) return cap_round_up(tb * nrhs, 2);
+  return cap_potrs_ctr_ints(n) + 2 * potrs_ldy(n) * nrhs;          // 2 x ctr_ints ints = ctr_ints doubles
+}
+static int potrs_run(const double* R, int64_t ldr, int64_t n, const double* Inv, int64_t tb, bool one, const double* B, int64_t ldb,
+                     double* X, int64_t ldx, int64_t nrhs, double* scr, const int* info, hipStream_t s) {
+  if (one) {
+    const int64_t cw = cap_potrs_ctr_ints(n), ldy = potrs_ldy(n);
+    int* ctr = reinterpret_cast<int*>(scr);
+    double* Y = scr + cw; double* S = Y + ldy * nrhs;
+    CAP_HIP(hipMemsetAsync(ctr, 0, sizeof(int) * 2 * cw, s));       // every counter of both launches, every call
+    CAP_TRY(cap_potrs_subst(1, n, nrhs, R, ldr, Inv, B, ldb, Y, ldy, S, ldy, ctr, info, s));
+    return cap_potrs_subst(0, n, nrhs, R, ldr, Inv, Y, ldy, X, ldx, S, ldy, ctr + cw, nullptr, s);
+  }
+  if (X != B) CAP_TRY(cap_copy_rect(B, ldb, X, ldx, n, nrhs, s));
+  const int ctag = cap_plain_device_ptr(X) ? 0 : CAP_TAG_NO_ATOMIC;
+  CAP_TRY(cap_trsm_apply(CAP_LEFT, CAP_TRANS, n, nrhs, R, ldr, Inv, tb, X, ldx, scr, s, ctag));
+  CAP_TRY(cap_trsm_apply(CAP_LEFT, CAP_NOTRANS, n, nrhs, R, ldr, Inv, tb, X, ldx, scr, s, ctag));
+  return cap_potrs_nan_fill(X, ldx, n, nrhs, info, s);
+}
+// (re)allocate a plan buffer of at least `elems` doubles; the old one may still be in use by work on the stream
+static int potrs_grow(double** buf, int64_t* have, int64_t elems) {
+  if (*buf && *have >= elems) return CAP_OK;
+  if (*buf) { CAP_HIP(hipDeviceSynchronize()); (void)hipFree(*buf); *buf = nullptr; *have = 0; }
+  CAP_HIP(hipMalloc((void**)buf, sizeof(double) * elems));
+  *have = elems;
+  return CAP_OK;
+}
+
+int cap_cholinv_solve(cap_cholinv_plan* p, const double* B, int64_t ldb, double* X, int64_t ldx, int64_t nrhs, void* stream) {
+  if (!p) return CAP_ERR_ARG;
+  if (p->dist) return CAP_ERR_UNSUPPORTED;      // multi-rank plans (and the "cyclic_c" layout, which only they have)
+  const int64_t n = p->n;
+  if (nrhs < 0 || (nrhs > 0 && (!B || !X || ldb < n || ldx < n))) return CAP_ERR_ARG;
+  if (p->gen == 0) return CAP_ERR_ARG;          // no factor to solve with
+  if (nrhs == 0) return CAP_OK;
+  hipStream_t s = cap_stream(stream);
+  const bool one = p->solve_kernel && nrhs <= 16;
+  const int64_t tb = one ? cap_potrs_block() : cap_trsm_block(n), nblk = cap_ceil_div(n, tb);
+  if (p->sv_inv_gen != p->gen || p->sv_inv_tb != tb) {
+    CAP_TRY(potrs_grow(&p->sv_inv, &p->sv_inv_elems, nblk * tb * tb + cap_trsm_prepare_work(tb)));
+    CAP_TRY(cap_trsm_prepare(p->R, p->ldr, n, tb, p->sv_inv, p->sv_inv + nblk * tb * tb, s));
+    p->sv_inv_gen = p->gen; p->sv_inv_tb = tb;
+  }
+  CAP_TRY(potrs_grow(&p->sv_work, &p->sv_work_elems, potrs_scratch_elems(n, nrhs, one, tb)));
+  return potrs_run(p->R, p->ldr, n, p->sv_inv, tb, one, B, ldb, X, ldx, nrhs, p->sv_work, p->info_dev, s);
+}
+
+// work: [solve scratch][block inverses][their TRTRI scratch]
+static bool dpotrs_one(int64_t nrhs) { return nrhs <= 16; }
+int64_t cap_dpotrs_work_size(int64_t n, int64_t nrhs) {
+  if (n <= 0 || nrhs <= 0) return 0;
+  const bool one = dpotrs_one(nrhs);
+  const int64_t tb = one ? cap_potrs_block() : cap_trsm_block(n);
+  return cap_round_up(potrs_scratch_elems(n, nrhs, one, tb), 2) + cap_ceil_div(n, tb) * tb * tb + cap_trsm_prepare_work(tb) + 8;
+}
+
+int cap_dpotrs(int uplo, int64_t n, int64_t nrhs, const double* R, int64_t ldr, double* B, int64_t ldb, double* work, void* stream) {
+  if (n < 0 || nrhs < 0 || (n > 0 && nrhs > 0 && (!R || !B || !work || ldr < n || ldb < n))) return CAP_ERR_ARG;
+  if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrf
+  if (n == 0 || nrhs == 0) return CAP_OK;
+  hipStream_t s = cap_stream(stream);
+  const bool one = dpotrs_one(nrhs);
+  const int64_t tb = one ? cap_potrs_block() : cap_trsm_block(n);
+  double* scr = work;
+  double* Inv = work + cap_round_up(potrs_scratch_elems(n, nrhs, one, tb), 2);
+  CAP_TRY(cap_trsm_prepare(R, ldr, n, tb, Inv, Inv + cap_ceil_div(n, tb) * tb * tb, s));
+  return potrs_run(R, ldr, n, Inv, tb, one, B, ldb, B, ldb, nrhs, scr, nullptr, s);
 }
 
 // B = alpha op(T) B  or  alpha B op(T)  (blas::engine::_trmm, blas/interface.hpp:61-79): the upper triangle is copied

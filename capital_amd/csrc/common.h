@@ -180,6 +180,14 @@ int cap_trsm_apply(int side, int trans, int64_t m, int64_t n, const double* T, i
 // gemm.hip: the streaming product with an fp32 operand (n <= 8, m >= 1024)
 int cap_skinny_f32a_launch(int transa, int64_t m, int64_t n, int64_t k, double alpha, const float* A32, int64_t lda, const double* B, int64_t ldb,
                            double beta, double* C, int64_t ldc, hipStream_t stream);
+// potrs.hip: one substitution of the fp64 solve in one launch + its recovery launch (fwd = 1: R^T Out = In, 0: R Out = In; nrhs <= 16;
+// Inv = the inverses of R's diagonal blocks of cap_potrs_block() rows; ctr: cap_potrs_ctr_ints(n) ints the caller zeroed on `s`;
+// info != NULL and != 0: Out is NaN); the NaN fill of the blocked path
+int64_t cap_potrs_block();
+int64_t cap_potrs_ctr_ints(int64_t n);
+int cap_potrs_subst(int fwd, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* Inv, const double* In, int64_t ldin,
+                    double* Out, int64_t ldout, double* S, int64_t lds, int* ctr, const int* info, hipStream_t s);
+int cap_potrs_nan_fill(double* X, int64_t ldx, int64_t n, int64_t nrhs, const int* info, hipStream_t s);
 int cap_rec_cholinv_full(double* R, int64_t ldr, double* Ri, int64_t ldi, int64_t n, double* W, int64_t wcap, int* info,
                          hipStream_t s, int64_t info_base);
 int64_t cap_rec_work_size(int64_t n);

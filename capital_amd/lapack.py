@@ -1,5 +1,6 @@
 """lapack::engine mirror (reference src/lapack/engine.h:23-102, src/lapack/interface.h:49-59).
 
+_potrs (A X = B with the factor of _potrf) has no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -30,6 +31,7 @@ class Diag(enum.IntEnum):
 class Method(enum.IntEnum):
     AlapackPotrf = 0x0
     AlapackTrtri = 0x1
+    AlapackPotrs = 0x2          # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
 
@@ -37,6 +39,12 @@ class Method(enum.IntEnum):
 class ArgPack_potrf:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPotrf
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_potrs:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotrs
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -57,6 +65,16 @@ class engine:
         st = L.cap_dpotrf(int(srcPackage.uplo), n, dptr(matrixA), lda, info.data_ptr(), dptr(work), cur_stream(stream))
         _lib.check(st, "lapack::engine::_potrf")
         return int(info.item())
+
+    @staticmethod
+    def _potrs(matrixR, matrixB, n, nrhs, ldr, ldb, srcPackage, stream=None):
+        """B (n x nrhs, ld ldb) <- A^-1 B with A = R^T R, R the upper factor _potrf left (ld ldr)."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        work = scratch(L.cap_dpotrs_work_size(n, nrhs), matrixB)
+        st = L.cap_dpotrs(int(srcPackage.uplo), n, nrhs, dptr(matrixR), ldr, dptr(matrixB), ldb, dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrs")
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

@@ -76,8 +76,9 @@ int64_t cap_dtrmm_work_size(int side, int64_t m, int64_t n);
 
 /* Real triangular solve (not in the reference, which inverts then multiplies - SURVEY 2b;
  * trsm/diaginvert/diaginvert.hpp:7-10 is a static_assert stub).  Solves
- * op(T) X = alpha B (LEFT) or X op(T) = alpha B (RIGHT) in place; T upper, non-unit.  Done as
- * "invert the triangle (recursive TRTRI), then one MFMA GEMM" - upstream's invert-then-multiply.
+ * op(T) X = alpha B (LEFT) or X op(T) = alpha B (RIGHT) in place; T upper, non-unit.  Done as a
+ * blocked substitution: only the diagonal blocks (width <= 512) are inverted (recursive TRTRI), then
+ * per block step one MFMA GEMM with the block inverse and one GEMM update of the remaining rows.
  * `work`: device scratch >= cap_dtrsm_work_size doubles.                                   */
 int cap_dtrsm(int side, int uplo, int trans, int64_t m, int64_t n, double alpha, const double* T,
               int64_t ldt, double* B, int64_t ldb, double* work, void* stream);
@@ -89,6 +90,14 @@ int64_t cap_dtrsm_work_size(int side, int64_t m, int64_t n);
  * non-positive pivot.  `work`: device scratch >= cap_dpotrf_work_size(n) doubles.         */
 int cap_dpotrf(int uplo, int64_t n, double* A, int64_t lda, int* info, double* work, void* stream);
 int64_t cap_dpotrf_work_size(int64_t n);
+
+/* lapack-style POTRS beside cap_dpotrf (not in the reference, whose trsm/diaginvert/diaginvert.hpp:7-10 is a stub):
+ * A X = B with A = R^T R, R upper (the output of cap_dpotrf; the other triangle is not referenced), B (n x nrhs) overwritten by X.
+ * uplo = LOWER -> CAP_ERR_UNSUPPORTED, as for cap_dpotrf.  `work`: device scratch >= cap_dpotrs_work_size(n, nrhs) doubles.
+ * Same two pieces as cap_cholinv_solve, the inverses of R's diagonal blocks computed into `work` on every call.              */
+int cap_dpotrs(int uplo, int64_t n, int64_t nrhs, const double* R, int64_t ldr, double* B, int64_t ldb,
+               double* work, void* stream);
+int64_t cap_dpotrs_work_size(int64_t n, int64_t nrhs);
 
 /* lapack::engine::_trtri - lapack/interface.h:52-53, interface.hpp:45-58 (LAPACKE_dtrtri).
  * In-place inverse of the triangular n x n block (non-unit).  work >= cap_dtrtri_work_size. */
@@ -318,6 +327,17 @@ int cap_cholinv_get_Rinv_desc(cap_cholinv_plan* plan, cap_desc* Rinv, void* stre
 /* device pointers to the resident factors (leading dimension returned through *ld).        */
 double* cap_cholinv_R_ptr(cap_cholinv_plan* plan, int64_t* ld);
 double* cap_cholinv_Rinv_ptr(cap_cholinv_plan* plan, int64_t* ld);
+/* A X = B with the factor of the plan's LAST factor call (any complete_inv).  B, X: n x nrhs, column-major,
+ * device memory; X == B (in place) is allowed.  Asynchronous on `stream`, no host synchronisation.
+ * Multi-rank plans and the "cyclic_c" layout return CAP_ERR_UNSUPPORTED.  If the last factor reported
+ * info != 0, X is filled with NaN (read the pivot with cap_cholinv_info).  A plan that was never factored: CAP_ERR_ARG.
+ * The first solve after a factor call inverts R's diagonal blocks and keeps them.  nrhs <= 16: one launch per substitution
+ * (forward R^T Y = B into plan scratch, backward R X = Y), workgroups claiming the blocks' diagonal steps and tile products from a
+ * ticket counter, each launch followed by a recovery launch that redoes the substitution on one workgroup if a workgroup of it
+ * gave up waiting (counted by cap_solve_fallbacks); option "solve_kernel" = 0 sends these to the blocked path that more
+ * right-hand sides take (cap_dtrsm's substitution: MFMA GEMMs per block step).                                              */
+int cap_cholinv_solve(cap_cholinv_plan* plan, const double* B, int64_t ldb, double* X, int64_t ldx,
+                      int64_t nrhs, void* stream);
 /* host-readable status of the last factor: 0, or 1-based index of the failing pivot.  A launch of the one-launch
  * diagonal-block chain (option "chain_coop") whose workgroups were never all resident gives up after ~3 s of polling, and the
  * recovery launch behind it restores that diagonal block and re-runs it on two workgroups (counted in option
@@ -348,6 +368,11 @@ int64_t cap_cholinv_get_option(cap_cholinv_plan* plan, const char* key);
  * TEST HOOK - the next `count` chain launches on the current device give up at their first meeting, so the recovery path runs.   */
 int64_t cap_chain_fallbacks(void);
 int cap_chain_inject_timeouts(int count);
+/* The same two diagnostics for the one-launch substitutions of cap_cholinv_solve / cap_dpotrs: substitutions of this process that the
+ * recovery launch finished on the current device (synchronises the device); TEST HOOK - the next `count` one-launch substitutions on
+ * the current device give up at their first wait.                                                                                  */
+int64_t cap_solve_fallbacks(void);
+int cap_solve_inject_timeouts(int count);
 /* Live measurement of the dominant kernel (trailing-update DSYRK) of the LAST factor call, enabled
  * with cap_cholinv_set_option(plan, "profile", 1): number of launches, their summed duration in ms
  * (HIP events recorded on the stream each launch went to) and summed algorithmic flops
