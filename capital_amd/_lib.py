@@ -33,6 +33,9 @@ SIGNATURES = {
     "cap_dpotrs_work_size": (i64, [i64, i64]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
+    "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),
+    "cap_dpotri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
+    "cap_dpotri_work_size": (i64, [i64]),
     "cap_desc_create": (cint, [C.POINTER(ptr), i64, i64, i64, i64]),
     "cap_desc_create_view": (cint, [C.POINTER(ptr), i64, i64, i64, i64, ptr, i64]),
     "cap_desc_create_bc": (cint, [C.POINTER(ptr), i64, i64, i64, cint, cint, cint, cint, ptr, i64]),
@@ -97,6 +100,8 @@ SIGNATURES = {
     "cap_cholinv_R_ptr": (ptr, [ptr, C.POINTER(i64)]),
     "cap_cholinv_Rinv_ptr": (ptr, [ptr, C.POINTER(i64)]),
     "cap_cholinv_solve": (cint, [ptr, ptr, i64, ptr, i64, i64, ptr]),
+    "cap_cholinv_inverse": (cint, [ptr, ptr, i64, cint, ptr]),
+    "cap_cholinv_logdet": (cint, [ptr, ptr, ptr]),
     "cap_cholinv_info": (cint, [ptr, ptr, C.POINTER(i64)]),
     "cap_cholinv_set_option": (cint, [ptr, C.c_char_p, i64]),
     "cap_cholinv_get_option": (i64, [ptr, C.c_char_p]),

@@ -4,6 +4,7 @@
     cholinv.factor(A, pack, topo)                                   # A: matrix (read-only)
     R = cholinv.construct_R(pack, topo); Rinv = cholinv.construct_Rinv(pack, topo)
     X = cholinv.solve(B, pack)                                      # A X = B with the factor of the last factor call
+    Ainv = cholinv.inverse(pack); ld = cholinv.logdet(pack)         # A^-1 = R^-1 R^-T and log det A = 2 sum log r_ii of that factor
 
 `info` keeps upstream's four user knobs.  complete_inv = -1 is the documented extension:
 blocked right-looking Cholesky (real TRSM/SYRK, no explicit inverse) - the headline
@@ -136,3 +137,29 @@ def solve(B, args, X=None):
     _lib.check(_lib.lib().cap_cholinv_solve(args._plan, B.data_ptr(), B.ld(), X.data_ptr(), X.ld(), nrhs, cur_stream()),
                "cholinv::solve")
     return X
+
+
+def inverse(args, out=None, fill=True):
+    """A^-1 = R^-1 R^-T of the factor `cholinv.factor` left in `args` (single-GPU plans, any complete_inv; not in the reference, which
+    stops at R and R^-1).  out: an n x n matrix, or None for a new one.  fill=True: both triangles; fill=False: only the upper triangle
+    of `out` is written.  Asynchronous on the current stream.  complete_inv = 0 / -1 plans keep an n x n inverse of R from the first
+    call after a factor call on.  A failing pivot of the last factor call leaves the written window NaN (args.last_info() reports it)."""
+    if args._plan is None:
+        raise _lib.CapitalError("cholinv.inverse needs a plan that cholinv.factor has filled")
+    n = args._n
+    if out is None:
+        out = matrix(n, n, 1, 1, rect)
+    elif out.num_rows_global() != n or out.num_columns_global() != n:
+        raise _lib.CapitalError("out must be %d x %d" % (n, n))
+    _lib.check(_lib.lib().cap_cholinv_inverse(args._plan, out.data_ptr(), out.ld(), 1 if fill else 0, cur_stream()), "cholinv::inverse")
+    return out
+
+
+def logdet(args):
+    """log det A = 2 sum log r_ii of the last factor call as a Python float (NaN when that factor failed).  The sum is formed on the
+    device in a fixed order; returning it to the host SYNCHRONISES the current stream."""
+    if args._plan is None:
+        raise _lib.CapitalError("cholinv.logdet needs a plan that cholinv.factor has filled")
+    out = torch.empty(1, dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()))
+    _lib.check(_lib.lib().cap_cholinv_logdet(args._plan, out.data_ptr(), cur_stream()), "cholinv::logdet")
+    return float(out.item())

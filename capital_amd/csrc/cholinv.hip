@@ -400,6 +400,9 @@ struct cap_cholinv_plan {
   int64_t gen; int solve_kernel;
   double* sv_inv; int64_t sv_inv_elems, sv_inv_tb, sv_inv_gen;
   double* sv_work; int64_t sv_work_elems;
+  // inverse (cap_cholinv_inverse) of the plans that do not hold all of R^-1 (complete_inv = 0 / -1): an n x n copy of R inverted in place
+  // by the first call after a factor call (pi_gen == gen: still valid), followed by TRTRI's scratch.  Allocated on first use.
+  double* pi_inv; int64_t pi_elems, pi_ld, pi_gen;
 };
 
 namespace {
@@ -1160,6 +1163,7 @@ int cap_cholinv_plan_destroy(cap_cholinv_plan* p) {
   if (p->info_dev) (void)hipFree(p->info_dev);
   if (p->sv_inv) (void)hipFree(p->sv_inv);
   if (p->sv_work) (void)hipFree(p->sv_work);
+  if (p->pi_inv) (void)hipFree(p->pi_inv);
   if (p->streams_ready) {
     cap_stream_destroy(p->s_panel);
     for (int i = 0; i < 2; i++) { (void)hipEventDestroy(p->ev_panel[i]); (void)hipEventDestroy(p->ev_update[i]); }
@@ -1575,6 +1579,58 @@ int cap_dpotrs(int uplo, int64_t n, int64_t nrhs, const double* R, int64_t ldr, 
   double* Inv = work + cap_round_up(potrs_scratch_elems(n, nrhs, one, tb), 2);
   CAP_TRY(cap_trsm_prepare(R, ldr, n, tb, Inv, Inv + cap_ceil_div(n, tb) * tb * tb, s));
   return potrs_run(R, ldr, n, Inv, tb, one, B, ldb, B, ldb, nrhs, scr, nullptr, s);
+}
+
+// ---- POTRI: A^-1 = R^-1 R^-T, the triangular inverse followed by the triangular product of lauum.hip (LAPACK's dtrtri + dlauum); log det A
+// The product reads only the upper triangle of its operand, so the plan's resident R^-1 (complete_inv = 1: ldi = n rounded up to even,
+// a hipMalloc'ed and therefore 16-byte aligned buffer whose strictly lower triangle the plan zeroed once and no kernel writes) is read
+// in place: no copy, no zero fill.  The other plans invert a zero-lower copy of R once per factor call.
+int cap_cholinv_inverse(cap_cholinv_plan* p, double* out, int64_t ld, int fill, void* stream) {
+  if (!p || !out || fill < 0 || fill > 1) return CAP_ERR_ARG;
+  if (p->dist) return CAP_ERR_UNSUPPORTED;      // multi-rank plans (and the "cyclic_c" layout, which only they have)
+  const int64_t n = p->n;
+  if (ld < n) return CAP_ERR_ARG;
+  if (p->gen == 0) return CAP_ERR_ARG;          // no factor to invert
+  hipStream_t s = cap_stream(stream);
+  const double* Ri = p->Rinv; int64_t ldi = p->ldi;
+  if (p->complete_inv != 1) {
+    const int64_t ldn = cap_round_up(n, 2), need = ldn * n + rec_work_size(n);
+    if (!p->pi_inv) {
+      if (hipMalloc((void**)&p->pi_inv, sizeof(double) * need) != hipSuccess) { (void)hipGetLastError(); p->pi_inv = nullptr; return CAP_ERR_ALLOC; }
+      p->pi_elems = need; p->pi_ld = ldn; p->pi_gen = 0;
+    }
+    if (p->pi_gen != p->gen) {
+      CAP_TRY(cap_copy_window(p->R, 0, p->ldr, 0, 0, p->pi_inv, 0, ldn, 0, 0, n, n, 1, 1, stream));
+      CAP_TRY(rec_trtri(p->pi_inv, ldn, n, p->pi_inv + ldn * n, rec_work_size(n), CAP_LEAF_MAX, s));
+      p->pi_gen = p->gen;
+    }
+    Ri = p->pi_inv; ldi = ldn;
+  }
+  CAP_TRY(cap_lauum_launch(n, Ri, ldi, out, ld, s));
+  if (fill) CAP_TRY(cap_mirror_upper(out, ld, n, s));
+  return cap_tri_nan_fill(out, ld, n, fill ? 0 : 1, p->info_dev, s);
+}
+
+int cap_cholinv_logdet(cap_cholinv_plan* p, double* logdet_dev, void* stream) {
+  if (!p || !logdet_dev) return CAP_ERR_ARG;
+  if (p->dist) return CAP_ERR_UNSUPPORTED;
+  if (p->gen == 0) return CAP_ERR_ARG;
+  return cap_logdet_launch(p->R, p->ldr, p->n, p->info_dev, logdet_dev, cap_stream(stream));
+}
+
+// work: [n x n zero-lower copy of R, inverted in place (ld = n rounded up to even)][TRTRI's scratch]
+int64_t cap_dpotri_work_size(int64_t n) { return n <= 0 ? 0 : cap_round_up(n, 2) * n + rec_work_size(n); }
+
+int cap_dpotri(int uplo, int64_t n, double* A, int64_t lda, double* work, void* stream) {
+  if (n < 0 || (n > 0 && (!A || lda < n || !work))) return CAP_ERR_ARG;
+  if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrf
+  if (n == 0) return CAP_OK;
+  hipStream_t s = cap_stream(stream);
+  const int64_t ldt = cap_round_up(n, 2);
+  double* T = work; double* W = work + ldt * n;
+  CAP_TRY(cap_copy_window(A, 0, lda, 0, 0, T, 0, ldt, 0, 0, n, n, 1, 1, stream));
+  CAP_TRY(rec_trtri(T, ldt, n, W, rec_work_size(n), CAP_LEAF_MAX, s));
+  return cap_lauum_launch(n, T, ldt, A, lda, s);
 }
 
 // B = alpha op(T) B  or  alpha B op(T)  (blas::engine::_trmm, blas/interface.hpp:61-79): the upper triangle is copied

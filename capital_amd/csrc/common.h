@@ -188,6 +188,13 @@ int64_t cap_potrs_ctr_ints(int64_t n);
 int cap_potrs_subst(int fwd, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* Inv, const double* In, int64_t ldin,
                     double* Out, int64_t ldout, double* S, int64_t lds, int* ctr, const int* info, hipStream_t s);
 int cap_potrs_nan_fill(double* X, int64_t ldx, int64_t n, int64_t nrhs, const int* info, hipStream_t s);
+// lauum.hip: upper triangle of C = W W^T, W upper triangular (its strictly lower triangle is never used, C's never written; any n, leading
+// dimension and alignment; W and C must not overlap); the strictly lower triangle of X from its upper one; NaN over the n x n window
+// (tri = 1: its upper triangle) when *info != 0; 2 sum log R_ii into ONE device double (NaN when info != NULL and *info != 0)
+int cap_lauum_launch(int64_t n, const double* W, int64_t ldw, double* C, int64_t ldc, hipStream_t stream);
+int cap_mirror_upper(double* X, int64_t ld, int64_t n, hipStream_t stream);
+int cap_tri_nan_fill(double* X, int64_t ld, int64_t n, int tri, const int* info, hipStream_t stream);
+int cap_logdet_launch(const double* R, int64_t ldr, int64_t n, const int* info, double* out, hipStream_t stream);
 int cap_rec_cholinv_full(double* R, int64_t ldr, double* Ri, int64_t ldi, int64_t n, double* W, int64_t wcap, int* info,
                          hipStream_t s, int64_t info_base);
 int64_t cap_rec_work_size(int64_t n);

@@ -1,6 +1,6 @@
 """lapack::engine mirror (reference src/lapack/engine.h:23-102, src/lapack/interface.h:49-59).
 
-_potrs (A X = B with the factor of _potrf) has no counterpart upstream.
+_potrs (A X = B with the factor of _potrf) and _potri (A^-1 from that factor) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -32,6 +32,7 @@ class Method(enum.IntEnum):
     AlapackPotrf = 0x0
     AlapackTrtri = 0x1
     AlapackPotrs = 0x2          # extension: not in the reference's enum
+    AlapackPotri = 0x3          # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
 
@@ -45,6 +46,12 @@ class ArgPack_potrf:
 class ArgPack_potrs:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPotrs
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_potri:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotri
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -75,6 +82,16 @@ class engine:
         work = scratch(L.cap_dpotrs_work_size(n, nrhs), matrixB)
         st = L.cap_dpotrs(int(srcPackage.uplo), n, nrhs, dptr(matrixR), ldr, dptr(matrixB), ldb, dptr(work), cur_stream(stream))
         _lib.check(st, "lapack::engine::_potrs")
+
+    @staticmethod
+    def _potri(matrixA, n, lda, srcPackage, stream=None):
+        """The upper triangle of A (n x n, ld lda; the factor R _potrf left) <- that of A^-1 = R^-1 R^-T; the other triangle is untouched."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        work = scratch(L.cap_dpotri_work_size(n), matrixA)
+        st = L.cap_dpotri(int(srcPackage.uplo), n, dptr(matrixA), lda, dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potri")
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

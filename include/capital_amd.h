@@ -104,6 +104,18 @@ int64_t cap_dpotrs_work_size(int64_t n, int64_t nrhs);
 int cap_dtrtri(int uplo, int64_t n, double* A, int64_t lda, double* work, void* stream);
 int64_t cap_dtrtri_work_size(int64_t n);
 
+/* LAPACK dlauum, out of place (not in the reference): upper triangle of C = W W^T, W upper triangular non-unit.  The strictly lower
+ * triangle of W is not referenced, the strictly lower triangle of C is not written.  W and C must not overlap (CAP_ERR_ARG).
+ * uplo = LOWER -> CAP_ERR_UNSUPPORTED.  n^3 / 3 flops on the LDS-DMA MFMA kernel when ldw is even and W 16-byte aligned (any n); an
+ * odd ldw or an unaligned W goes through a copy and the dense-K product (three times the flops).                               */
+int cap_dlauum(int uplo, int64_t n, const double* W, int64_t ldw, double* C, int64_t ldc, void* stream);
+
+/* LAPACK dpotri beside cap_dpotrf (= dtrtri + dlauum): A holds R (upper, from cap_dpotrf); on return its upper triangle holds that of
+ * A^-1 = R^-1 R^-T.  The strictly lower triangle is neither read nor written.  uplo = LOWER -> CAP_ERR_UNSUPPORTED.
+ * work >= cap_dpotri_work_size(n) doubles (an n x n inverse + TRTRI's own scratch).                                             */
+int cap_dpotri(int uplo, int64_t n, double* A, int64_t lda, double* work, void* stream);
+int64_t cap_dpotri_work_size(int64_t n);
+
 /* ------------------------------------------------------------------------------------
  * Matrix descriptor helpers (replaces src/matrix/: generators, serialize, structure)
  * ---------------------------------------------------------------------------------- */
@@ -338,6 +350,16 @@ double* cap_cholinv_Rinv_ptr(cap_cholinv_plan* plan, int64_t* ld);
  * right-hand sides take (cap_dtrsm's substitution: MFMA GEMMs per block step).                                              */
 int cap_cholinv_solve(cap_cholinv_plan* plan, const double* B, int64_t ldb, double* X, int64_t ldx,
                       int64_t nrhs, void* stream);
+/* A^-1 of the plan's LAST factor call into out (n x n, column-major, device).  fill = 0: upper triangle only, the rest of out untouched;
+ * fill = 1: both triangles (the lower one is a copy of the upper one).  Asynchronous on `stream`, no host synchronisation.  Same rules as
+ * cap_cholinv_solve: any complete_inv; multi-rank plans and "cyclic_c" -> CAP_ERR_UNSUPPORTED; never factored -> CAP_ERR_ARG; last factor
+ * info != 0 -> the n x n window (fill = 0: its upper triangle) is NaN.  complete_inv = 1: one triangular product (cap_dlauum's kernel)
+ * from the resident R^-1.  complete_inv = 0 / -1: the first call after a factor call inverts a copy of R and keeps it until the next
+ * factor call - n^2 more doubles of device memory (plus TRTRI's scratch), allocated on the first call (CAP_ERR_ALLOC if that fails).  */
+int cap_cholinv_inverse(cap_cholinv_plan* plan, double* out, int64_t ld, int fill, void* stream);
+/* log det A = 2 sum log R_ii of the last factor call, written to ONE double in device memory; asynchronous, deterministic (fixed
+ * summation order: two calls give the same bits).  NaN if the last factor failed.  Same UNSUPPORTED / ARG rules.                 */
+int cap_cholinv_logdet(cap_cholinv_plan* plan, double* logdet_dev, void* stream);
 /* host-readable status of the last factor: 0, or 1-based index of the failing pivot.  A launch of the one-launch
  * diagonal-block chain (option "chain_coop") whose workgroups were never all resident gives up after ~3 s of polling, and the
  * recovery launch behind it restores that diagonal block and re-runs it on two workgroups (counted in option
