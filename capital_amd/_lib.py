@@ -36,6 +36,8 @@ SIGNATURES = {
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),
     "cap_dpotri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dpotri_work_size": (i64, [i64]),
+    "cap_dgemm_tall_tn_work_size": (i64, [i64, i64, i64]),
+    "cap_dgemm_tall_tn": (cint, [i64, i64, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr]),
     "cap_desc_create": (cint, [C.POINTER(ptr), i64, i64, i64, i64]),
     "cap_desc_create_view": (cint, [C.POINTER(ptr), i64, i64, i64, i64, ptr, i64]),
     "cap_desc_create_bc": (cint, [C.POINTER(ptr), i64, i64, i64, cint, cint, cint, cint, ptr, i64]),
@@ -176,6 +178,8 @@ SIGNATURES = {
     "cap_cacqr_Q_ptr": (ptr, [ptr, C.POINTER(i64)]),
     "cap_cacqr_R_ptr": (ptr, [ptr, C.POINTER(i64)]),
     "cap_cacqr_info": (cint, [ptr, ptr, C.POINTER(i64)]),
+    "cap_cacqr_apply_qt": (cint, [ptr, ptr, i64, i64, ptr, i64, ptr]),
+    "cap_cacqr_solve": (cint, [ptr, ptr, i64, i64, ptr, i64, ptr]),
 }
 
 

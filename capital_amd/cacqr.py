@@ -3,6 +3,7 @@
     pack = cacqr.info(num_iter, cholinv.info(...))      # num_iter: 1 = CholeskyQR, 2 = CholeskyQR2
     cacqr.factor(A, pack, topo.rect(c))                 # A: local element-cyclic piece: rows over d, columns over c
     Q = cacqr.construct_Q(pack, topo); R = cacqr.construct_R(pack, topo)
+    X = cacqr.solve(pack, B)                            # least squares min ||A X - B||: R^-1 (Q^T B); cacqr.apply_Qt(pack, B) = Q^T B
 
 c == 1 (cacqr.hpp:229, the shape of BASELINE config 4): the 1D path - rows cyclic over all ranks, one Gram all-reduce
 per sweep.  c > 1: the 3D (c == d) / tunable-grid (d > c) path of cacqr.hpp:75-170 on the c x d x c grid of a
@@ -113,3 +114,44 @@ def dense_R(args):
     st = _lib.lib().cap_copy_window(r, 0, ld.value, 0, 0, out.data_ptr(), 0, out.ld(), 0, 0, n, n, 1, 1, cur_stream())
     _lib.check(st, "dense_R")
     return out
+
+
+def _rhs(args, B):
+    """(address, leading dimension, nrhs) of the local m_local x nrhs piece of the right-hand sides: a `matrix`, or a device tensor of shape
+    (m_local,) / (m_local, nrhs) - used in place when it is column-major, through a column-major copy otherwise"""
+    if args._plan is None:
+        raise _lib.CapitalError("cacqr: no factor call yet (nothing to apply or solve with)")
+    m_local = args._shape[0]
+    if isinstance(B, matrix):
+        if B.num_rows_local() != m_local:
+            raise _lib.CapitalError("right-hand sides have %d local rows, the factored matrix %d" % (B.num_rows_local(), m_local))
+        return B.data_ptr(), B.ld(), B.num_columns_local(), B
+    if not isinstance(B, torch.Tensor) or B.device.type != "cuda" or B.dtype != torch.float64:
+        raise _lib.CapitalError("right-hand sides must be a matrix or an fp64 device tensor; no CPU path")
+    t = B.reshape(-1, 1) if B.dim() == 1 else B
+    if t.dim() != 2 or t.shape[0] != m_local:
+        raise _lib.CapitalError("right-hand sides must be (m_local,) or (m_local, nrhs) with m_local = %d" % m_local)
+    if not (t.stride(0) == 1 and (t.shape[1] == 1 or t.stride(1) >= m_local)):
+        t = t.t().contiguous().t()                      # column-major copy, ld = m_local
+    return t.data_ptr(), (t.stride(1) if t.shape[1] > 1 else max(m_local, 1)), t.shape[1], t
+
+
+def _apply(entry, what, args, B):
+    b, ldb, nrhs, keep = _rhs(args, B)
+    n = args._shape[1] if not args._grid else args._gn
+    out = matrix(nrhs, n, 1, 1, rect)
+    _lib.check(getattr(_lib.lib(), entry)(args._plan, b, ldb, nrhs, out.data_ptr(), out.ld(), cur_stream()), what)
+    del keep
+    return out
+
+
+def apply_Qt(args, B, CommInfo=None):
+    """Z = Q^T B of the last factor call (cap_cacqr_apply_qt): B is this rank's m_local x nrhs piece of the right-hand sides (rows
+    distributed like A's), the result a fresh replicated n x nrhs matrix.  1D plans only."""
+    return _apply("cap_cacqr_apply_qt", "cacqr::apply_Qt", args, B)
+
+
+def solve(args, B, CommInfo=None):
+    """X = argmin ||A X - B||_F = R^-1 (Q^T B) of the last factor call (cap_cacqr_solve), a fresh replicated n x nrhs matrix; all NaN
+    when the factorization failed (last_info() != 0).  1D plans only."""
+    return _apply("cap_cacqr_solve", "cacqr::solve", args, B)

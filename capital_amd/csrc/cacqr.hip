@@ -24,6 +24,7 @@
 //   Q_new[=y, =x] = sum_z Qz * Rinv[=z, =x]: layer z contributes its term, ncclAllReduce over `depth`
 //                                                                          (summa TRMM + depth all-reduce, :107-111)
 // which is `A2 - Q1 R12` done right for every block at once (upstream's solve() has the sign flipped).
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -46,6 +47,9 @@ struct cap_cacqr_plan {
   int* info_dev;
   double* gram_work;      // n == 256: one partial-Gram slab per workgroup of gram256
   bool gi_clean;          // Gi's never-written blocks are known to be zero (see sweep)
+  // least-squares solve (1D plans): gen counts the factor calls; the slab partials of Q^T B (16 right-hand sides), the inverses of R's
+  // diagonal blocks (of factor call sv_gen) + their TRTRI scratch, and the block temp of the substitution - all allocated on first use
+  int64_t gen; double* qt_work; double* sv_inv; int64_t sv_gen; double* sv_tmp; int64_t sv_tmp_elems;
   // grid path: m, n above are the GLOBAL column count / local row count of the dense n x n work; nl = n / c local columns
   cap_topo* topo; int c, d, x, y, z; int64_t nl;
   double* Qz; double* Gblk; double* Gall; double* Rip; double* Rpiece;
@@ -185,6 +189,9 @@ int cap_cacqr_plan_destroy(cap_cacqr_plan* p) {
   if (p->W) (void)hipFree(p->W);
   if (p->info_dev) (void)hipFree(p->info_dev);
   if (p->gram_work) (void)hipFree(p->gram_work);
+  if (p->qt_work) (void)hipFree(p->qt_work);
+  if (p->sv_inv) (void)hipFree(p->sv_inv);
+  if (p->sv_tmp) (void)hipFree(p->sv_tmp);
   if (p->Qz) (void)hipFree(p->Qz);
   if (p->Gblk) (void)hipFree(p->Gblk);
   delete p;
@@ -196,6 +203,7 @@ int cap_cacqr_factor(cap_cacqr_plan* p, const double* A, int64_t lda, void* stre
   hipStream_t s = cap_stream(stream);
   const int64_t n = p->n;
   CAP_HIP(hipMemsetAsync(p->info_dev, 0, sizeof(int), s));
+  p->gen++;
   if (p->topo) {
     // invoke_3d (cacqr.hpp:195-215): sweep, [save R1, sweep, R = R2 R1]; R stays dense and replicated, the caller's
     // cyclic piece is cut out by cap_cacqr_R_piece
@@ -244,6 +252,71 @@ int cap_cacqr_info(cap_cacqr_plan* p, void* stream, int64_t* info) {
   CAP_HIP(hipStreamSynchronize(cap_stream(stream)));
   *info = h;
   return h == 0 ? CAP_OK : CAP_ERR_NOT_SPD;
+}
+
+// ---- least-squares solve on the factorization (not in the reference): min ||A x - b||_2 is x = R^-1 (Q^T b).  Q^T B streams the plan's
+// Q once (csrc/cqr_solve.hip: the row range split over the whole chip), the n x nrhs block is summed over the ranks, and R X = Z is the
+// blocked substitution of cap_dtrsm on the plan's final R (= R2 R1 for CholeskyQR2), the inverses of R's diagonal blocks kept per factor
+// call.  Measured at 2^21 x 256, 8 right-hand sides (profiles/r09_cacqr_solve.txt): the product 1.03 ms, everything after it 0.05 ms with the
+// kept block inverses (two block steps of small GEMMs at n = 256) against ~ 0.12 ms for cap_dtrsm, which inverts the blocks on every call.  The
+// one-launch substitution of potrs.hip would need its own block inverses, counters and recovery launch for what is left of those 0.05 ms.
+static int cacqr_solve_check(cap_cacqr_plan* p, const double* B, int64_t ldb, int64_t nrhs, double* Z, int64_t ldz) {
+  if (!p) return CAP_ERR_ARG;
+  if (p->topo) return CAP_ERR_UNSUPPORTED;                   // grid plans: Q's columns are spread over the process row
+  if (nrhs < 0 || (nrhs > 0 && (!B || !Z || ldb < p->m || ldz < p->n))) return CAP_ERR_ARG;
+  if (p->gen == 0) return CAP_ERR_ARG;                       // no factor to solve with
+  return CAP_OK;
+}
+
+static int cacqr_apply_qt(cap_cacqr_plan* p, const double* B, int64_t ldb, int64_t nrhs, double* Z, int64_t ldz, hipStream_t s) {
+  const int64_t m = p->m, n = p->n;
+  if (!p->qt_work) {
+    const int64_t w = std::max<int64_t>(cap_dgemm_tall_tn_work_size(m, n, 16), 2);
+    if (hipMalloc((void**)&p->qt_work, sizeof(double) * w) != hipSuccess) { (void)hipGetLastError(); p->qt_work = nullptr; return CAP_ERR_ALLOC; }
+  }
+  CapRange range("CQR::applyQt");
+  CAP_TRY(cap_dgemm_tall_tn(m, n, nrhs, p->Q[p->cur], p->ldq, B, ldb, Z, ldz, p->qt_work, (void*)s));
+  if (p->comm) {                                             // the n x nrhs block, summed over the ranks
+    if (ldz == n) CAP_TRY(cap_comm_allreduce_sum(p->comm, Z, n * nrhs, (void*)s));
+    else for (int64_t j = 0; j < nrhs; j++) CAP_TRY(cap_comm_allreduce_sum(p->comm, Z + j * ldz, n, (void*)s));
+  }
+  return CAP_OK;
+}
+
+int cap_cacqr_apply_qt(cap_cacqr_plan* p, const double* B, int64_t ldb, int64_t nrhs, double* Z, int64_t ldz, void* stream) {
+  CAP_TRY(cacqr_solve_check(p, B, ldb, nrhs, Z, ldz));
+  if (nrhs == 0) return CAP_OK;
+  hipStream_t s = cap_stream(stream);
+  CAP_TRY(cacqr_apply_qt(p, B, ldb, nrhs, Z, ldz, s));
+  return cap_potrs_nan_fill(Z, ldz, p->n, nrhs, p->info_dev, s);
+}
+
+int cap_cacqr_solve(cap_cacqr_plan* p, const double* B, int64_t ldb, int64_t nrhs, double* X, int64_t ldx, void* stream) {
+  CAP_TRY(cacqr_solve_check(p, B, ldb, nrhs, X, ldx));
+  if (nrhs == 0) return CAP_OK;
+  hipStream_t s = cap_stream(stream);
+  const int64_t n = p->n, tb = cap_trsm_block(n), nblk = cap_ceil_div(n, tb);
+  if (!p->sv_inv) {
+    if (hipMalloc((void**)&p->sv_inv, sizeof(double) * (nblk * tb * tb + cap_trsm_prepare_work(tb))) != hipSuccess) {
+      (void)hipGetLastError(); p->sv_inv = nullptr; return CAP_ERR_ALLOC;
+    }
+    p->sv_gen = 0;
+  }
+  const int64_t need = cap_round_up(tb * nrhs, 2);
+  if (!p->sv_tmp || p->sv_tmp_elems < need) {                // (the old one may still be in use by work on the stream)
+    if (p->sv_tmp) { CAP_HIP(hipDeviceSynchronize()); (void)hipFree(p->sv_tmp); p->sv_tmp = nullptr; p->sv_tmp_elems = 0; }
+    const int64_t elems = std::max<int64_t>(need, tb * 16);
+    if (hipMalloc((void**)&p->sv_tmp, sizeof(double) * elems) != hipSuccess) { (void)hipGetLastError(); p->sv_tmp = nullptr; return CAP_ERR_ALLOC; }
+    p->sv_tmp_elems = elems;
+  }
+  CAP_TRY(cacqr_apply_qt(p, B, ldb, nrhs, X, ldx, s));
+  CapRange range("CQR::solveR");
+  if (p->sv_gen != p->gen) {
+    CAP_TRY(cap_trsm_prepare(p->R, n, n, tb, p->sv_inv, p->sv_inv + nblk * tb * tb, s));
+    p->sv_gen = p->gen;
+  }
+  CAP_TRY(cap_trsm_apply(CAP_LEFT, CAP_NOTRANS, n, nrhs, p->R, n, p->sv_inv, tb, X, ldx, p->sv_tmp, s, cap_plain_device_ptr(X) ? 0 : CAP_TAG_NO_ATOMIC));
+  return cap_potrs_nan_fill(X, ldx, n, nrhs, p->info_dev, s);
 }
 
 }  // extern "C"

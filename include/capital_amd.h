@@ -116,6 +116,19 @@ int cap_dlauum(int uplo, int64_t n, const double* W, int64_t ldw, double* C, int
 int cap_dpotri(int uplo, int64_t n, double* A, int64_t lda, double* work, void* stream);
 int64_t cap_dpotri_work_size(int64_t n);
 
+/* Z[n x nrhs] = Q^T B for a tall-skinny Q (m x n, m >> n) and a few right-hand sides B (m x nrhs), all column-major in device memory
+ * (not in the reference: the expensive step of a least-squares solve on a QR factorization, cap_cacqr_solve below).  Z is overwritten,
+ * its padding rows (ldz > n) are not touched; Z must not overlap Q, B or work.
+ * n % 16 == 0, n <= 256, m % 8 == 0, even ldq / ldb, 16-byte aligned Q and B, nrhs <= 48: the streaming kernel of csrc/cqr_solve.hip - the
+ * ROWS of Q are split into slabs over the whole chip, Q is read once per 16 right-hand sides, the slabs' partial sums go through `work` and
+ * are added in a fixed order (no floating-point atomics: two calls give the same bits; accumulators restart every 64 rows).  Bound by HBM.
+ * Every other shape (other n, a ragged m, odd leading dimensions, unaligned operands, more right-hand sides) is the same product
+ * through the 128 x 128 tile kernels of cap_dgemm(CAP_TRANS, CAP_NOTRANS, n, nrhs, m): correct, and several times slower for a few
+ * right-hand sides (they are padded to 128).  work >= cap_dgemm_tall_tn_work_size(m, n, nrhs) doubles.                               */
+int64_t cap_dgemm_tall_tn_work_size(int64_t m, int64_t n, int64_t nrhs);
+int cap_dgemm_tall_tn(int64_t m, int64_t n, int64_t nrhs, const double* Q, int64_t ldq, const double* B, int64_t ldb, double* Z,
+                      int64_t ldz, double* work, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Matrix descriptor helpers (replaces src/matrix/: generators, serialize, structure)
  * ---------------------------------------------------------------------------------- */
@@ -557,6 +570,19 @@ int cap_cacqr_factor(cap_cacqr_plan* plan, const double* A, int64_t lda, void* s
 double* cap_cacqr_Q_ptr(cap_cacqr_plan* plan, int64_t* ld);
 double* cap_cacqr_R_ptr(cap_cacqr_plan* plan, int64_t* ld);
 int cap_cacqr_info(cap_cacqr_plan* plan, void* stream, int64_t* info);
+/* Least squares on the plan's LAST factor call (not in the reference, which stops at Q and R): B is the caller's local m_local x nrhs piece
+ * of the right-hand sides, rows distributed like A's; Z, X: n x nrhs, replicated on every rank.  Column-major device memory, asynchronous
+ * on `stream`, no host synchronisation; any nrhs >= 0, both num_iter values.
+ *   cap_cacqr_apply_qt  Z = Q^T B: cap_dgemm_tall_tn on the plan's Q, then the all-reduce of the n x nrhs block over the plan's
+ *                       communicator (none for comm == NULL).
+ *   cap_cacqr_solve     X = argmin ||A X - B||_F = R^-1 (Q^T B): the above into X, then the blocked substitution of cap_dtrsm on the
+ *                       plan's final R; the inverses of R's diagonal blocks are computed by the first solve after a factor call and kept.
+ * Plans of the 1D path only: a grid plan (cap_cacqr_plan_create_grid) returns CAP_ERR_UNSUPPORTED.  A plan that was never factored, or
+ * a bad argument: CAP_ERR_ARG.  If the last factor reported info != 0, Z / X are filled with NaN and the call returns CAP_OK, as
+ * cap_cholinv_solve does (read the pivot with cap_cacqr_info).  The first call allocates the slab buffer of the product (sized for 16
+ * right-hand sides) and the solve's scratch inside the plan (CAP_ERR_ALLOC if that fails); cap_cacqr_plan_destroy frees them.          */
+int cap_cacqr_apply_qt(cap_cacqr_plan* plan, const double* B, int64_t ldb, int64_t nrhs, double* Z, int64_t ldz, void* stream);
+int cap_cacqr_solve(cap_cacqr_plan* plan, const double* B, int64_t ldb, int64_t nrhs, double* X, int64_t ldx, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Mixed-precision Cholesky solve (BASELINE config 5; not in the reference, whose solve path is the
