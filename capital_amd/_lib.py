@@ -178,6 +178,7 @@ SIGNATURES = {
     "cap_cacqr_Q_ptr": (ptr, [ptr, C.POINTER(i64)]),
     "cap_cacqr_R_ptr": (ptr, [ptr, C.POINTER(i64)]),
     "cap_cacqr_info": (cint, [ptr, ptr, C.POINTER(i64)]),
+    "cap_cacqr_shift": (cint, [ptr, C.POINTER(C.c_double), ptr]),
     "cap_cacqr_apply_qt": (cint, [ptr, ptr, i64, i64, ptr, i64, ptr]),
     "cap_cacqr_solve": (cint, [ptr, ptr, i64, i64, ptr, i64, ptr]),
 }

@@ -5,6 +5,10 @@
     Q = cacqr.construct_Q(pack, topo); R = cacqr.construct_R(pack, topo)
     X = cacqr.solve(pack, B)                            # least squares min ||A X - B||: R^-1 (Q^T B); cacqr.apply_Qt(pack, B) = Q^T B
 
+Extension (not in the reference, like lapack.AlapackPotrs): num_iter 3 and 4 are shifted CholeskyQR3 - one / two shifted, equilibrated sweeps
+in front of CholeskyQR2 for matrices CholeskyQR2 alone cannot factor (kappa >~ 1e8; include/capital_amd.h states the supported region).  1D path
+only.  `info.shift()` is the shift of the last factor call, `factor_robust` escalates num_iter 2 -> 3 -> 4 until the factorization succeeds.
+
 c == 1 (cacqr.hpp:229, the shape of BASELINE config 4): the 1D path - rows cyclic over all ranks, one Gram all-reduce
 per sweep.  c > 1: the 3D (c == d) / tunable-grid (d > c) path of cacqr.hpp:75-170 on the c x d x c grid of a
 `topo.rect` bundle (csrc/cacqr.hip: sweep_grid)."""
@@ -24,24 +28,25 @@ class info:
         self._plan = None
         self._shape = None
         self._grid = False
+        self._plan_iter = None            # the num_iter the plan was created with (factor_robust changes num_iter)
 
     def _ensure(self, m_local, n, comm):
-        if self._plan is not None and self._shape == (m_local, n) and not self._grid:
+        if self._plan is not None and self._shape == (m_local, n) and not self._grid and self._plan_iter == self.num_iter:
             return
         self._release()
         h = C.c_void_p()
         _lib.check(_lib.lib().cap_cacqr_plan_create(C.byref(h), m_local, n, self.num_iter, comm), "cap_cacqr_plan_create")
-        self._plan, self._shape, self._grid = h, (m_local, n), False
+        self._plan, self._shape, self._grid, self._plan_iter = h, (m_local, n), False, self.num_iter
 
     def _ensure_grid(self, A, topo):
         key = (A.num_rows_local(), A.num_columns_local())
-        if self._plan is not None and self._shape == key and self._grid:
+        if self._plan is not None and self._shape == key and self._grid and self._plan_iter == self.num_iter:
             return
         self._release()
         h = C.c_void_p()
         _lib.check(_lib.lib().cap_cacqr_plan_create_grid(C.byref(h), A.num_rows_global(), A.num_columns_global(), self.num_iter,
                                                          topo.handle), "cap_cacqr_plan_create_grid")
-        self._plan, self._shape, self._grid = h, key, True
+        self._plan, self._shape, self._grid, self._plan_iter = h, key, True, self.num_iter
 
     def _release(self):
         if self._plan is not None:
@@ -51,6 +56,14 @@ class info:
     def last_info(self):
         v = C.c_int64(0)
         _lib.check_info(_lib.lib().cap_cacqr_info(self._plan, cur_stream(), C.byref(v)), "cap_cacqr_info")
+        return v.value
+
+    def shift(self):
+        """the shift s = 11 (m n + n (n + 1)) 2^-53 n of the last factor call (m: the global row count); 0.0 for num_iter <= 2"""
+        if self._plan is None:
+            raise _lib.CapitalError("cacqr: no factor call yet")
+        v = C.c_double(0.0)
+        _lib.check(_lib.lib().cap_cacqr_shift(self._plan, C.byref(v), cur_stream()), "cap_cacqr_shift")
         return v.value
 
     def __del__(self):
@@ -73,6 +86,22 @@ def factor(A, args, CommInfo=None):
     comm = getattr(CommInfo, "world", None) if CommInfo is not None else None
     args._ensure(A.num_rows_local(), A.num_columns_local(), comm)
     _lib.check(_lib.lib().cap_cacqr_factor(args._plan, A.data_ptr(), A.ld(), cur_stream()), "cacqr::factor")
+
+
+def factor_robust(A, args, CommInfo=None, max_iter=4):
+    """factor with the cheapest variant that succeeds: `factor` with num_iter 2, then 3, then 4, until last_info() == 0.  Returns the num_iter
+    it ended on (args.num_iter is set to it) and leaves `args` usable by solve, apply_Qt, construct_Q and construct_R; raises CapitalError when
+    max_iter is exhausted.  Each attempt reads info back (one host synchronisation per attempt).  On several ranks every rank takes the same
+    decision without talking to the others: the all-reduced Gram matrix, and with it every pivot and `info`, is bit-identical on every rank.
+    1D path only (the grid plans refuse num_iter > 2)."""
+    last = None
+    for it in range(2, int(max_iter) + 1):
+        args.num_iter = it
+        factor(A, args, CommInfo)
+        last = args.last_info()
+        if last == 0:
+            return it
+    raise _lib.CapitalError("cacqr::factor_robust: no factorization up to num_iter = %d (last info %s)" % (int(max_iter), last))
 
 
 def construct_Q(args, CommInfo=None):

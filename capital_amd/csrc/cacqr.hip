@@ -9,6 +9,9 @@
 //           R = chol(G), Rinv = R^-1   in-LDS / recursive cholinv (potrf; memcpy; trtri upstream)
 //           Q = Q * Rinv      DGEMM "NN" streaming pass (upstream: dtrmm Right/Upper/NoTrans)
 //   CholeskyQR2: second sweep on Q, then R = R2 * R1 (cacqr.hpp:180-188).
+//   num_iter 3 / 4 (not in the reference): shifted CholeskyQR3 - one / two SHIFTED sweeps in front of CholeskyQR2.  A shifted sweep is this
+//   sweep with the conditioning launches of cqr_shift.hip around the factorization (Gram equilibrated to unit diagonal, diagonal 1 + s; the
+//   scaling undone on R and R^-1); R = R_last ... R_2 R_1.  1D plans only.
 // Q ping-pongs between two device buffers so the streaming GEMM is never in place.
 //
 // Grid path (cacqr.hpp:75-170 sweep_3d / sweep_tune, :44-73 solve, :195-215 invoke_3d) on a topo::rect bundle
@@ -39,6 +42,10 @@ int64_t cap_rec_work_size(int64_t n);
 int64_t cap_gram256_work(int64_t m);
 int cap_gram256_launch(const double* Q, int64_t ld, int64_t m, double* G, int64_t ldg, double* work, hipStream_t s);
 int cap_qrapply256_launch(const double* Qin, int64_t ldin, const double* Ri, double* Qout, int64_t ldout, int64_t m, hipStream_t s);
+// cqr_shift.hip: the conditioning launches of a shifted sweep
+int cap_scqr_set_rows(double* m_global, int64_t m_local, hipStream_t s);
+int cap_scqr_equilibrate(double* G, int64_t ldg, int64_t n, const double* m_global, double* d, double* shift, hipStream_t s);
+int cap_scqr_unscale(double* R, int64_t ldr, double* Ri, int64_t ldi, int64_t n, const double* d, hipStream_t s);
 
 struct cap_cacqr_plan {
   int64_t m, n; int num_iter; cap_comm* comm;
@@ -47,6 +54,9 @@ struct cap_cacqr_plan {
   int* info_dev;
   double* gram_work;      // n == 256: one partial-Gram slab per workgroup of gram256
   bool gi_clean;          // Gi's never-written blocks are known to be zero (see sweep)
+  // shifted sweeps (num_iter > 2, 1D plans): the second buffer of the running product R_k ... R_1, the column scales d (n), the GLOBAL row
+  // count and the shift of the last factor call as device words; rows_ready: the row count has been summed over the ranks (once per plan)
+  double* P; double* dscale; double* rows_dev; double* shift_dev; bool rows_ready;
   // least-squares solve (1D plans): gen counts the factor calls; the slab partials of Q^T B (16 right-hand sides), the inverses of R's
   // diagonal blocks (of factor call sv_gen) + their TRTRI scratch, and the block temp of the substitution - all allocated on first use
   int64_t gen; double* qt_work; double* sv_inv; int64_t sv_gen; double* sv_tmp; int64_t sv_tmp_elems;
@@ -58,7 +68,7 @@ struct cap_cacqr_plan {
 namespace {
 // one CholeskyQR sweep: Qout = Qin * chol(Qin^T Qin)^-1.  The first sweep reads the caller's A in place (no A -> Q copy:
 // serialize<rect,rect>(A -> Q) of cacqr.hpp:226 only exists upstream because its TRMM is in place)
-int sweep(cap_cacqr_plan* p, const double* Qin, int64_t ldin, double* Qout, hipStream_t s) {
+int sweep(cap_cacqr_plan* p, const double* Qin, int64_t ldin, double* Qout, hipStream_t s, bool shifted = false) {
   const int64_t m = p->m, n = p->n;
   // Gram: upper triangle of Q^T Q (cacqr.hpp:15), full square zero-initialised so the all-reduce moves
   // a dense n x n block like NoSerialize::compute_gram (policy.h:22)
@@ -74,16 +84,41 @@ int sweep(cap_cacqr_plan* p, const double* Qin, int64_t ldin, double* Qout, hipS
     }
     CAP_TRY(cap_comm_allreduce_sum(p->comm, p->G, n * n, (void*)s));
   }
+  // shifted sweep: G <- D^-1 G D^-1 with diagonal 1 + s (D = diag(sqrt(G_jj)) into p->dscale first: the diagonal is both operand and result)
+  if (shifted) CAP_TRY(cap_scqr_equilibrate(p->G, n, n, p->rows_dev, p->dscale, p->shift_dev, s));
   // R = chol(G) in place (upper), Gi = R^-1.  The 64-blocked path (n = 256) rewrites every entry of Gi it ever wrote (diagonal
   // blocks with their zero lower parts, the off-diagonal blocks above them) and never touches the blocks below: one zero-fill
   // per plan is enough there
   if (!(k256 && p->gi_clean)) { CAP_TRY(cap_zero_rect(p->Gi, n, n, n, s)); p->gi_clean = k256; }
   CAP_TRY(cap_rec_cholinv_full(p->G, n, p->Gi, n, n, p->W, p->wcap, p->info_dev, s));
+  if (shifted) CAP_TRY(cap_scqr_unscale(p->G, n, p->Gi, n, n, p->dscale, s));     // R_k = R' D, R_k^-1 = D^-1 R'^-1
   // Q <- Q * R^-1 (cacqr.hpp:24-25)
   // tag 8: R^-1 is upper triangular -> a column tile only contracts the rows above its diagonal block
   CapRange range("CQR::formR");                   // cacqr.hpp:106-115 (the TRMM with R^-1)
   if (k256) CAP_TRY(cap_qrapply256_launch(Qin, ldin, p->Gi, Qout, p->ldq, m, s));
   else CAP_TRY(cap_gemm_launch(CAP_NOTRANS, CAP_NOTRANS, m, n, n, 1.0, Qin, ldin, p->Gi, n, 0.0, Qout, p->ldq, 0, s, 8));
+  return CAP_OK;
+}
+// num_iter 3 / 4: num_iter - 2 shifted sweeps, then the two sweeps of CholeskyQR2; R = R_last ... R_1, the running product alternating
+// between R1 and P.  The global row count of the shift is summed over the plan's communicator by the first call (ranks may hold unequal
+// m_local; a shift computed from the local count would give every rank another R)
+int factor_shifted(cap_cacqr_plan* p, const double* A, int64_t lda, hipStream_t s) {
+  const int64_t n = p->n;
+  if (!p->rows_ready) {
+    CAP_TRY(cap_scqr_set_rows(p->rows_dev, p->m, s));
+    if (p->comm) CAP_TRY(cap_comm_allreduce_sum(p->comm, p->rows_dev, 1, (void*)s));
+    p->rows_ready = true;                                              // (ordered by this stream: a plan is driven from one stream, capital_amd.h)
+  }
+  const double* in = A; int64_t ldin = lda;
+  double* acc = p->R1;
+  for (int k = 0; k < p->num_iter; k++) {
+    CAP_TRY(sweep(p, in, ldin, p->Q[k & 1], s, k < p->num_iter - 2));
+    p->cur = k & 1; in = p->Q[k & 1]; ldin = p->ldq;
+    if (k == 0) { CAP_TRY(cap_copy_rect(p->G, n, p->R1, n, n, n, s)); continue; }
+    double* dst = k == p->num_iter - 1 ? p->R : (acc == p->R1 ? p->P : p->R1);
+    CAP_TRY(cap_gemm_launch(CAP_NOTRANS, CAP_NOTRANS, n, n, n, 1.0, p->G, n, acc, n, 0.0, dst, n, 0, s));
+    acc = dst;
+  }
   return CAP_OK;
 }
 // gathered[z'][x'] blocks (nl x nl each, block (z', x') = G[rows = z' mod c, cols = x' mod c]) -> dense n x n
@@ -129,7 +164,8 @@ extern "C" {
 // qr::cacqr on the c x d x c grid of a topo::rect bundle (cacqr.hpp:217-248 with c > 1): A_local is the
 // ceil(M / d) x (N / c) element-cyclic piece; N must be a multiple of c (a zero-padded column would make the Gram singular).
 int cap_cacqr_plan_create_grid(cap_cacqr_plan** plan, int64_t m_global, int64_t n_global, int num_iter, cap_topo* topo) {
-  if (!plan || !topo || m_global <= 0 || n_global <= 0 || num_iter < 1 || num_iter > 2) return CAP_ERR_ARG;
+  if (!plan || !topo || m_global <= 0 || n_global <= 0 || num_iter < 1 || num_iter > 4) return CAP_ERR_ARG;
+  if (num_iter > 2) return CAP_ERR_UNSUPPORTED;                        // shifted sweeps: 1D plans only
   if (cap_topo_get(topo, 9) != 1) return CAP_ERR_ARG;                  // topo::rect
   const int c = cap_topo_get(topo, 2), d = cap_topo_get(topo, 3);
   if (n_global % c) return CAP_ERR_UNSUPPORTED;
@@ -163,7 +199,7 @@ int cap_cacqr_plan_create_grid(cap_cacqr_plan** plan, int64_t m_global, int64_t 
 }
 
 int cap_cacqr_plan_create(cap_cacqr_plan** plan, int64_t m_local, int64_t n, int num_iter, cap_comm* comm) {
-  if (!plan || m_local <= 0 || n <= 0 || num_iter < 1 || num_iter > 2) return CAP_ERR_ARG;
+  if (!plan || m_local <= 0 || n <= 0 || num_iter < 1 || num_iter > 4) return CAP_ERR_ARG;
   cap_cacqr_plan* p = new (std::nothrow) cap_cacqr_plan();
   if (!p) return CAP_ERR_ALLOC;
   memset(p, 0, sizeof(*p));
@@ -172,12 +208,13 @@ int cap_cacqr_plan_create(cap_cacqr_plan** plan, int64_t m_local, int64_t n, int
   p->wcap = cap_rec_work_size(n);
   hipError_t e = hipSuccess;
   for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipMalloc((void**)&p->Q[i], sizeof(double) * p->ldq * n);
-  if (e == hipSuccess) e = hipMalloc((void**)&p->G, sizeof(double) * n * n * 4);
+  if (e == hipSuccess) e = hipMalloc((void**)&p->G, sizeof(double) * (n * n * 5 + n + 2));
   if (e == hipSuccess) e = hipMalloc((void**)&p->W, sizeof(double) * p->wcap);
   if (e == hipSuccess) e = hipMalloc((void**)&p->info_dev, sizeof(int));
   if (e == hipSuccess && n == 256 && m_local % 128 == 0) e = hipMalloc((void**)&p->gram_work, sizeof(double) * cap_gram256_work(m_local));
   if (e != hipSuccess) { cap_cacqr_plan_destroy(p); return CAP_ERR_ALLOC; }
   p->Gi = p->G + n * n; p->R1 = p->G + 2 * n * n; p->R = p->G + 3 * n * n;
+  p->P = p->G + 4 * n * n; p->dscale = p->P + n * n; p->rows_dev = p->dscale + n; p->shift_dev = p->rows_dev + 1;
   *plan = p;
   return CAP_OK;
 }
@@ -219,6 +256,7 @@ int cap_cacqr_factor(cap_cacqr_plan* p, const double* A, int64_t lda, void* stre
     }
     return CAP_OK;
   }
+  if (p->num_iter > 2) return factor_shifted(p, A, lda, s);
   CAP_TRY(sweep(p, A, lda, p->Q[0], s));
   p->cur = 0;
   if (p->num_iter > 1) {
@@ -252,6 +290,16 @@ int cap_cacqr_info(cap_cacqr_plan* p, void* stream, int64_t* info) {
   CAP_HIP(hipStreamSynchronize(cap_stream(stream)));
   *info = h;
   return h == 0 ? CAP_OK : CAP_ERR_NOT_SPD;
+}
+
+// the shift s of the plan's last factor call (0 for num_iter <= 2 and before the first call); synchronises the stream
+int cap_cacqr_shift(cap_cacqr_plan* p, double* shift_host, void* stream) {
+  if (!p || !shift_host) return CAP_ERR_ARG;
+  hipStream_t s = cap_stream(stream);
+  *shift_host = 0.0;
+  if (p->num_iter > 2 && p->gen > 0 && !p->topo) CAP_HIP(hipMemcpyAsync(shift_host, p->shift_dev, sizeof(double), hipMemcpyDeviceToHost, s));
+  CAP_HIP(hipStreamSynchronize(s));
+  return CAP_OK;
 }
 
 // ---- least-squares solve on the factorization (not in the reference): min ||A x - b||_2 is x = R^-1 (Q^T b).  Q^T B streams the plan's

@@ -553,7 +553,25 @@ int cap_summa_dsyrk(cap_summa_plan* plan, int uplo, int trans, double alpha, con
 
 /* qr::cacqr<...>::info + factor, 1D path - cacqr.h:18-49, cacqr.hpp:5-29,172-193,217-248.
  * A is the local row-cyclic piece (m_local x n, column-major); R (n x n) is replicated;
- * num_iter = 1 (CholeskyQR) or 2 (CholeskyQR2).  comm == NULL -> single rank.              */
+ * num_iter = 1 (CholeskyQR) or 2 (CholeskyQR2).  comm == NULL -> single rank.
+ *
+ * num_iter = 3 or 4 (not in the reference; cap_cacqr_plan_create accepts num_iter 1 ... 4, anything else is CAP_ERR_ARG): shifted CholeskyQR3
+ * (Fukaya, Kannan, Nakatsukasa, Yamamoto, Yanagisawa, SIAM J. Sci. Comput. 2020) for matrices whose Gram matrix CholeskyQR2 cannot factor
+ * (kappa(A) >~ 1e8).  The first num_iter - 2 sweeps are SHIFTED, the last two are CholeskyQR2 unchanged.  A shifted sweep is a sweep - same
+ * Gram kernel, same all-reduce, same factorization, same Q R^-1 pass, on the caller's stream without a host synchronisation - with the Gram
+ * equilibrated in between: d_j = sqrt(G_jj), G_ij <- G_ij / (d_i d_j), diagonal set to 1 + s, and R_k = R' D, R_k^-1 = D^-1 R'^-1 behind the
+ * factorization; R = R_last ... R_1.  The shift is the closed form s = 11 (m n + n (n + 1)) 2^-53 n with m the GLOBAL row count (the plan sums
+ * m_local over its communicator once, on its first factor call): no norm reduction, bit-reproducible, and unaffected by column scaling.
+ * Supported region: one shifted sweep brings kappa down by about 1 / sqrt(s), CholeskyQR2 then needs kappa <~ 1e7 - 1e8.  The shift grows
+ * with m, so the reach shrinks with the row count: measured at n = 256 (profiles/r10_scqr.txt; largest kappa of the tested decades that ended
+ * with info == 0, residual < 1e-13, orthogonality < 1e-15)
+ *     m = 2^13: num_iter 3 up to kappa = 1e12, num_iter 4 up to 1e15;  m = 2^16: 1e11 / 1e14;  m = 2^21: 1e11 / 1e13
+ * (CholeskyQR2 alone: 1e8 at all three; the decade above each figure ended with info != 0).
+ * An input beyond that region - a shift too small for it - surfaces as info != 0 from cap_cacqr_info (and NaN from cap_cacqr_solve), never
+ * as a silently wrong Q: the last two sweeps are plain CholeskyQR2, whose Cholesky factorization meets a non-positive pivot.
+ * A plan is driven from ONE stream: what it keeps between calls on the device (the summed row count of the shift, buffers known to be zero) is
+ * ordered by that stream only; a caller that moves a plan to another stream orders the two streams itself (an event, a synchronisation).
+ * cap_cacqr_factor, _Q_ptr, _R_ptr, _info, _apply_qt and _solve keep their contracts for every num_iter.                              */
 typedef struct cap_cacqr_plan cap_cacqr_plan;
 int cap_cacqr_plan_create(cap_cacqr_plan** plan, int64_t m_local, int64_t n, int num_iter, cap_comm* comm);
 /* The 3D / tunable-grid path (cacqr.hpp:44-170: sweep_3d, sweep_tune, solve; invoke_3d :195-215) on a topo::rect
@@ -561,7 +579,8 @@ int cap_cacqr_plan_create(cap_cacqr_plan** plan, int64_t m_local, int64_t n, int
  * x mod c, replicated over the layers).  Row broadcast + Gram block + all-reduces over the process column, dense
  * Gram assembled on every rank, Cholesky factor and inverse computed redundantly per GPU, Q R^-1 as one term per
  * layer summed over `depth`.  Q_ptr is the local piece of Q, R_ptr the dense replicated R, cap_cacqr_R_piece the
- * c x c cyclic piece upstream keeps.                                                                              */
+ * c x c cyclic piece upstream keeps.  num_iter 1 or 2 only: a grid plan with num_iter 3 or 4 returns CAP_ERR_UNSUPPORTED (the
+ * shifted sweeps are built for the 1D path).                                                                      */
 int cap_cacqr_plan_create_grid(cap_cacqr_plan** plan, int64_t m_global, int64_t n_global, int num_iter, cap_topo* topo);
 int64_t cap_cacqr_local_cols(const cap_cacqr_plan* plan);
 int cap_cacqr_R_piece(cap_cacqr_plan* plan, double* out, int64_t ld, void* stream);
@@ -570,9 +589,12 @@ int cap_cacqr_factor(cap_cacqr_plan* plan, const double* A, int64_t lda, void* s
 double* cap_cacqr_Q_ptr(cap_cacqr_plan* plan, int64_t* ld);
 double* cap_cacqr_R_ptr(cap_cacqr_plan* plan, int64_t* ld);
 int cap_cacqr_info(cap_cacqr_plan* plan, void* stream, int64_t* info);
+/* The shift s of the plan's last factor call into *shift_host; 0.0 for plans with num_iter <= 2 and before the first factor call.
+ * Synchronises the stream.                                                                                                              */
+int cap_cacqr_shift(cap_cacqr_plan* plan, double* shift_host, void* stream);
 /* Least squares on the plan's LAST factor call (not in the reference, which stops at Q and R): B is the caller's local m_local x nrhs piece
  * of the right-hand sides, rows distributed like A's; Z, X: n x nrhs, replicated on every rank.  Column-major device memory, asynchronous
- * on `stream`, no host synchronisation; any nrhs >= 0, both num_iter values.
+ * on `stream`, no host synchronisation; any nrhs >= 0, every num_iter.
  *   cap_cacqr_apply_qt  Z = Q^T B: cap_dgemm_tall_tn on the plan's Q, then the all-reduce of the n x nrhs block over the plan's
  *                       communicator (none for comm == NULL).
  *   cap_cacqr_solve     X = argmin ||A X - B||_F = R^-1 (Q^T B): the above into X, then the blocked substitution of cap_dtrsm on the
