@@ -15,6 +15,7 @@
 // Never linked into the product; nothing here computes anything.
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -135,6 +136,15 @@ int shim_dump(const char* path) {
   return 0;
 }
 void shim_set_compute(int on) { compute = on; }
+// device names of every kernel the loaded object files registered, one per line (tests/test_blas3_paths.py: no instance without a case);
+// returns the length the whole list needs, writes at most cap - 1 characters of it
+long long shim_kernel_names(char* out, long long cap) {
+  std::lock_guard<std::mutex> lk(mu);
+  std::string all;
+  for (const auto& k : kernels) { all += k.second; all += '\n'; }
+  if (out && cap > 0) { const size_t n = std::min<size_t>(all.size(), (size_t)cap - 1); memcpy(out, all.data(), n); out[n] = 0; }
+  return (long long)all.size() + 1;
+}
 long long shim_unmodelled() { return unmodelled; }
 // an op of the test's own making on a stream (the stand-in collectives of a callback communicator); its access notes come first
 void shim_note_op(const char* name, void* stream) { std::lock_guard<std::mutex> lk(mu); note("OP %d %s", sid((hipStream_t)stream), name); flush_pending(name); }

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -79,10 +80,23 @@ void mma(Acc& c, int i0, int i1, int j0, int j1, const double* A, int64_t as_o, 
 
 constexpr int TB = 128, TK = 16;
 
+// run-time modes of the tile-kernel launches the models have executed, one line per launch (shim_gemm_modes below): the template instance is
+// in the kernel's name, these fields only travel in GemmArgs (tests/test_blas3_paths.py checks them against its case table)
+std::mutex modes_mu;
+std::vector<std::string> gemm_modes;
+void log_modes(const GemmArgs& g) {
+  char buf[256];
+  snprintf(buf, sizeof(buf), "ksplit=%d skip=%d stm=%d stn=%d sorder=%d etri=%d tri=%d bupper=%d aupt=%d aupn=%d usebuf=%d tm=%d tn=%d",
+           g.ksplit, g.skip, g.stm, g.stn, g.sorder, g.etri, g.tri, g.bupper, g.aupt, g.aupn, g.usebuf, g.tm, g.tn);
+  std::lock_guard<std::mutex> lk(modes_mu);
+  gemm_modes.emplace_back(buf);
+}
+
 // dgemm_kernel<A_KC, B_KC, EDGE, TAG>: the register-staged kernels (any shape)
 void k_dgemm(const std::string& name, void** a, unsigned gx, unsigned gy) {
   const GemmArgs g = arg<GemmArgs>(a, 0);
   const bool akc = tmpl(name, 0), bkc = tmpl(name, 1);
+  log_modes(g);
 #pragma omp parallel for collapse(2) schedule(dynamic)
   for (unsigned kz = 0; kz < gy; kz++)
     for (unsigned bx = 0; bx < gx; bx++) {
@@ -116,6 +130,7 @@ static long fault_seen = 0;
 void k_dgemm_dma(const std::string& name, void** a, unsigned gx, unsigned gy) {
   GemmArgs g = arg<GemmArgs>(a, 0);
   const bool amc = tmpl(name, 1), skip = tmpl(name, 4);
+  log_modes(g);
   static const char* fault = getenv("SHIM_FAULT");
   if (fault) {
     const int kind = atoi(fault); const char* c = strchr(fault, ':'); const long nth = c ? atol(c + 1) : 0;
@@ -736,6 +751,15 @@ void k_bf16_tn(void** a, unsigned gx, const int TB = 128, const int KG = 64) {
 #include <omp.h>
 // OpenMP threads of the CALLING thread's kernel models (a rank thread of a multi-rank case takes its share of the host cores)
 extern "C" void shim_set_threads(int n) { omp_set_num_threads(n < 1 ? 1 : n); }
+// the mode lines of the tile-kernel launches modelled since the last call, newline separated (at most cap - 1 characters); the log is cleared
+extern "C" long long shim_gemm_modes(char* out, long long cap) {
+  std::lock_guard<std::mutex> lk(modes_mu);
+  std::string all;
+  for (const auto& l : gemm_modes) { all += l; all += '\n'; }
+  gemm_modes.clear();
+  if (out && cap > 0) { const size_t n = std::min<size_t>(all.size(), (size_t)cap - 1); memcpy(out, all.data(), n); out[n] = 0; }
+  return (long long)all.size() + 1;
+}
 static int dispatch(const char* mangled, void** args, unsigned gx, unsigned gy, unsigned gz, unsigned bx);
 // SHIM_PROFILE=1: seconds per kernel model, printed when the process ends
 #include <chrono>
