@@ -36,6 +36,8 @@ SIGNATURES = {
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),
     "cap_dpotri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dpotri_work_size": (i64, [i64]),
+    "cap_dcholupdate": (cint, [cint, cint, i64, i64, ptr, i64, ptr, i64, ptr, ptr, ptr]),
+    "cap_dcholupdate_work_size": (i64, [i64, i64]),
     "cap_dgemm_tall_tn_work_size": (i64, [i64, i64, i64]),
     "cap_dgemm_tall_tn": (cint, [i64, i64, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr]),
     "cap_desc_create": (cint, [C.POINTER(ptr), i64, i64, i64, i64]),
@@ -104,6 +106,7 @@ SIGNATURES = {
     "cap_cholinv_solve": (cint, [ptr, ptr, i64, ptr, i64, i64, ptr]),
     "cap_cholinv_inverse": (cint, [ptr, ptr, i64, cint, ptr]),
     "cap_cholinv_logdet": (cint, [ptr, ptr, ptr]),
+    "cap_cholinv_update": (cint, [ptr, cint, ptr, i64, i64, ptr]),
     "cap_cholinv_info": (cint, [ptr, ptr, C.POINTER(i64)]),
     "cap_cholinv_set_option": (cint, [ptr, C.c_char_p, i64]),
     "cap_cholinv_get_option": (i64, [ptr, C.c_char_p]),
@@ -161,6 +164,8 @@ SIGNATURES = {
     "cap_chain_inject_timeouts": (cint, [cint]),
     "cap_solve_fallbacks": (i64, []),
     "cap_solve_inject_timeouts": (cint, [cint]),
+    "cap_update_fallbacks": (i64, []),
+    "cap_update_inject_timeouts": (cint, [cint]),
     "cap_bf16_update": (cint, [cint, i64, i64, i64, C.c_float, ptr, i64, ptr, i64, ptr, i64, cint, cint, ptr]),
     "cap_dmp_plan_create": (cint, [C.POINTER(ptr), i64, i64, i64, ptr]),
     "cap_dmp_plan_destroy": (cint, [ptr]),

@@ -5,6 +5,7 @@
     R = cholinv.construct_R(pack, topo); Rinv = cholinv.construct_Rinv(pack, topo)
     X = cholinv.solve(B, pack)                                      # A X = B with the factor of the last factor call
     Ainv = cholinv.inverse(pack); ld = cholinv.logdet(pack)         # A^-1 = R^-1 R^-T and log det A = 2 sum log r_ii of that factor
+    cholinv.update(V, pack); cholinv.downdate(V, pack)              # the resident factor follows A + V V^T / A - V V^T (V: n x k, k << n)
 
 `info` keeps upstream's four user knobs.  complete_inv = -1 is the documented extension:
 blocked right-looking Cholesky (real TRSM/SYRK, no explicit inverse) - the headline
@@ -163,3 +164,40 @@ def logdet(args):
     out = torch.empty(1, dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()))
     _lib.check(_lib.lib().cap_cholinv_logdet(args._plan, out.data_ptr(), cur_stream()), "cholinv::logdet")
     return float(out.item())
+
+
+def _thin(args, V):
+    """(address, leading dimension, k, keep-alive) of the n x k matrix V: a `matrix`, or an fp64 device tensor of shape (n,) / (n, k) - used
+    in place when it is column-major, through a column-major copy otherwise"""
+    n = args._n
+    if isinstance(V, matrix):
+        if V.num_rows_global() != n:
+            raise _lib.CapitalError("V has %d rows, the factor is %d x %d" % (V.num_rows_global(), n, n))
+        return V.data_ptr(), V.ld(), V.num_columns_global(), V
+    if not isinstance(V, torch.Tensor) or V.device.type != "cuda" or V.dtype != torch.float64:
+        raise _lib.CapitalError("V must be a matrix or an fp64 device tensor; no CPU path")
+    t = V.reshape(-1, 1) if V.dim() == 1 else V
+    if t.dim() != 2 or t.shape[0] != n:
+        raise _lib.CapitalError("V must be (n,) or (n, k) with n = %d" % n)
+    if not (t.stride(0) == 1 and (t.shape[1] == 1 or t.stride(1) >= n)):
+        t = t.t().contiguous().t()                      # column-major copy, ld = n
+    return t.data_ptr(), (t.stride(1) if t.shape[1] > 1 else max(n, 1)), t.shape[1], t
+
+
+def update(V, args, sign=+1):
+    """The resident factor of the last `cholinv.factor` becomes that of A + sign V V^T (sign = +1 / -1; LINPACK's dchud / dchdd) in
+    2 k n^2 flops instead of a new factorization.  V: n x k `matrix` or fp64 device tensor of shape (n,) / (n, k), not written.
+    Single-GPU plans with complete_inv = -1.  Asynchronous on the current stream; later solve / inverse / logdet calls use the new
+    factor.  A downdate that leaves the matrix indefinite reports its row through args.last_info(); the factor is lost then."""
+    if args._plan is None:
+        raise _lib.CapitalError("cholinv.update needs a plan that cholinv.factor has filled")
+    if sign not in (1, -1):
+        raise _lib.CapitalError("sign must be +1 or -1")
+    v, ldv, k, keep = _thin(args, V)
+    _lib.check(_lib.lib().cap_cholinv_update(args._plan, int(sign), v, ldv, k, cur_stream()), "cholinv::update")
+    del keep
+
+
+def downdate(V, args):
+    """`update` with sign = -1: the factor of A - V V^T."""
+    update(V, args, sign=-1)

@@ -403,6 +403,8 @@ struct cap_cholinv_plan {
   // inverse (cap_cholinv_inverse) of the plans that do not hold all of R^-1 (complete_inv = 0 / -1): an n x n copy of R inverted in place
   // by the first call after a factor call (pi_gen == gen: still valid), followed by TRTRI's scratch.  Allocated on first use.
   double* pi_inv; int64_t pi_elems, pi_ld, pi_gen;
+  // update / downdate (cap_cholinv_update): its scratch, allocated on first use; chud_kernel 1: one launch per pass, 0: stepwise
+  double* ud_work; int64_t ud_work_elems; int chud_kernel;
 };
 
 namespace {
@@ -1145,6 +1147,7 @@ int cap_cholinv_plan_create(cap_cholinv_plan** plan, int64_t n, int complete_inv
   p->inv_overlap = CAP_ENV("CAP_INV_OVERLAP") ? atoi(CAP_ENV("CAP_INV_OVERLAP")) : 1;
   p->inv_start_m = CAP_ENV("CAP_INV_START_M") ? atoll(CAP_ENV("CAP_INV_START_M")) : std::max<int64_t>(16384, n / 2);
   p->solve_kernel = 1;
+  p->chud_kernel = 1;
   int st = plan_alloc(p);
   if (st != CAP_OK) { cap_cholinv_plan_destroy(p); return st; }
   *plan = p;
@@ -1164,6 +1167,7 @@ int cap_cholinv_plan_destroy(cap_cholinv_plan* p) {
   if (p->sv_inv) (void)hipFree(p->sv_inv);
   if (p->sv_work) (void)hipFree(p->sv_work);
   if (p->pi_inv) (void)hipFree(p->pi_inv);
+  if (p->ud_work) (void)hipFree(p->ud_work);
   if (p->streams_ready) {
     cap_stream_destroy(p->s_panel);
     for (int i = 0; i < 2; i++) { (void)hipEventDestroy(p->ev_panel[i]); (void)hipEventDestroy(p->ev_update[i]); }
@@ -1190,6 +1194,7 @@ int cap_cholinv_set_option(cap_cholinv_plan* p, const char* key, int64_t value) 
   if (k == "chain_coop") { if (value < -1 || value > 256) return CAP_ERR_ARG; p->chain_coop = (int)value; return CAP_OK; }
   // nrhs <= 16 solves: 1 = the one-launch substitutions of potrs.hip (default), 0 = the blocked substitution of cap_dtrsm
   if (k == "solve_kernel") { if (value < 0 || value > 1) return CAP_ERR_ARG; p->solve_kernel = (int)value; return CAP_OK; }
+  if (k == "chud_kernel") { if (value < 0 || value > 1) return CAP_ERR_ARG; p->chud_kernel = (int)value; return CAP_OK; }
   if (p->dist) {
     if (k == "nb") {        // block width of the distribution: rebuild the inner plan
       if (value < 128 || value % 128) return CAP_ERR_ARG;
@@ -1269,6 +1274,7 @@ int64_t cap_cholinv_get_option(cap_cholinv_plan* p, const char* key) {
   if (k == "chain_coop") { if (p->chain_coop >= 0) return p->chain_coop; return cap_chain_coop_get(); }
   if (k == "chain_fallbacks") return cap_chain_fallbacks();
   if (k == "solve_kernel") return p->solve_kernel;
+  if (k == "chud_kernel") return p->chud_kernel;
   if (p->dist) {
     if (k == "complete_inv") return p->complete_inv;
     if (k == "split") return p->split;
@@ -1631,6 +1637,31 @@ int cap_dpotri(int uplo, int64_t n, double* A, int64_t lda, double* work, void* 
   CAP_TRY(cap_copy_window(A, 0, lda, 0, 0, T, 0, ldt, 0, 0, n, n, 1, 1, stream));
   CAP_TRY(rec_trtri(T, ldt, n, W, rec_work_size(n), CAP_LEAF_MAX, s));
   return cap_lauum_launch(n, T, ldt, A, lda, s);
+}
+
+// ---- rank-k update / downdate of the factor (LINPACK's dchud / dchdd, MATLAB's cholupdate): R'^T R' = R^T R + sign V V^T by the
+// row sweep of cholupdate.hip, in place on the upper triangle, 2 k n^2 flops and one pass over the triangle per 16 columns of V
+int64_t cap_dcholupdate_work_size(int64_t n, int64_t k) { return cap_chud_work_size(n, k); }
+
+int cap_dcholupdate(int uplo, int sign, int64_t n, int64_t k, double* R, int64_t ldr, const double* V, int64_t ldv, int* info,
+                    double* work, void* stream) {
+  if ((sign != 1 && sign != -1) || n < 0 || k < 0 || (n > 0 && k > 0 && (!R || !V || !work || ldr < n || ldv < n))) return CAP_ERR_ARG;
+  if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrf
+  if (n == 0 || k == 0) return CAP_OK;
+  return cap_chud_run(sign, n, k, R, ldr, V, ldv, info, 0, work, 1, cap_stream(stream));
+}
+
+int cap_cholinv_update(cap_cholinv_plan* p, int sign, const double* V, int64_t ldv, int64_t k, void* stream) {
+  if (!p) return CAP_ERR_ARG;
+  const int64_t n = p->n;
+  if ((sign != 1 && sign != -1) || k < 0 || (k > 0 && (!V || ldv < n))) return CAP_ERR_ARG;
+  if (p->dist) return CAP_ERR_UNSUPPORTED;             // multi-rank plans (and the "cyclic_c" layout, which only they have)
+  if (p->complete_inv >= 0) return CAP_ERR_UNSUPPORTED; // their resident R^-1 would go stale
+  if (p->gen == 0) return CAP_ERR_ARG;                 // no factor to update
+  if (k == 0) return CAP_OK;
+  CAP_TRY(potrs_grow(&p->ud_work, &p->ud_work_elems, cap_chud_work_size(n, k)));
+  p->gen++;                                            // the solve's block inverses and the cached inverse belong to the old factor
+  return cap_chud_run(sign, n, k, p->R, p->ldr, V, ldv, p->info_dev, 1, p->ud_work, p->chud_kernel, cap_stream(stream));
 }
 
 // B = alpha op(T) B  or  alpha B op(T)  (blas::engine::_trmm, blas/interface.hpp:61-79): the upper triangle is copied

@@ -188,6 +188,12 @@ int64_t cap_potrs_ctr_ints(int64_t n);
 int cap_potrs_subst(int fwd, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* Inv, const double* In, int64_t ldin,
                     double* Out, int64_t ldout, double* S, int64_t lds, int* ctr, const int* info, hipStream_t s);
 int cap_potrs_nan_fill(double* X, int64_t ldx, int64_t n, int64_t nrhs, const int* info, hipStream_t s);
+// cholupdate.hip: R'^T R' = R^T R + sign V V^T in place on the upper factor (k columns in passes of 16; one = 1: one launch per pass +
+// its recovery launch, 0: two launches per block row, same bits).  info_mode 0: `info` (may be NULL) is zeroed, then takes the first
+// failing row; 1: `info` is a plan's report - nonzero on entry leaves R and info alone (decided on the device)
+int64_t cap_chud_work_size(int64_t n, int64_t k);
+int cap_chud_run(int sign, int64_t n, int64_t k, double* R, int64_t ldr, const double* V, int64_t ldv, int* info, int info_mode,
+                 double* work, int one, hipStream_t s);
 // lauum.hip: upper triangle of C = W W^T, W upper triangular (its strictly lower triangle is never used, C's never written; any n, leading
 // dimension and alignment; W and C must not overlap); the strictly lower triangle of X from its upper one; NaN over the n x n window
 // (tri = 1: its upper triangle) when *info != 0; 2 sum log R_ii into ONE device double (NaN when info != NULL and *info != 0)

@@ -1,6 +1,7 @@
 """lapack::engine mirror (reference src/lapack/engine.h:23-102, src/lapack/interface.h:49-59).
 
-_potrs (A X = B with the factor of _potrf) and _potri (A^-1 from that factor) have no counterpart upstream.
+_potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor) and _cholupdate (that factor after A +- V V^T) have no
+counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -33,6 +34,7 @@ class Method(enum.IntEnum):
     AlapackTrtri = 0x1
     AlapackPotrs = 0x2          # extension: not in the reference's enum
     AlapackPotri = 0x3          # extension: not in the reference's enum
+    AlapackCholupdate = 0x4     # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
 
@@ -52,6 +54,12 @@ class ArgPack_potrs:
 class ArgPack_potri:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPotri
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_cholupdate:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackCholupdate
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -92,6 +100,20 @@ class engine:
         work = scratch(L.cap_dpotri_work_size(n), matrixA)
         st = L.cap_dpotri(int(srcPackage.uplo), n, dptr(matrixA), lda, dptr(work), cur_stream(stream))
         _lib.check(st, "lapack::engine::_potri")
+
+    @staticmethod
+    def _cholupdate(matrixR, matrixV, n, k, ldr, ldv, sign, srcPackage, stream=None):
+        """The upper factor R (n x n, ld ldr; what _potrf left) <- the factor of R^T R + sign V V^T, V n x k (ld ldv, not written),
+        sign = +1 / -1.  Returns info: 0, or the 1-based row at which a downdate found the matrix not positive definite (R is lost then)."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        work = scratch(L.cap_dcholupdate_work_size(n, k), matrixR)
+        info = torch.zeros(1, dtype=torch.int32, device=work.device)
+        st = L.cap_dcholupdate(int(srcPackage.uplo), int(sign), n, k, dptr(matrixR), ldr, dptr(matrixV), ldv, info.data_ptr(), dptr(work),
+                               cur_stream(stream))
+        _lib.check(st, "lapack::engine::_cholupdate")
+        return int(info.item())
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

@@ -116,6 +116,28 @@ int cap_dlauum(int uplo, int64_t n, const double* W, int64_t ldw, double* C, int
 int cap_dpotri(int uplo, int64_t n, double* A, int64_t lda, double* work, void* stream);
 int64_t cap_dpotri_work_size(int64_t n);
 
+/* Rank-k update (sign = +1) / downdate (sign = -1) of the factor beside cap_dpotrf (LINPACK's dchud / dchdd, MATLAB's cholupdate; not in
+ * the reference): R holds the upper factor of A = R^T R; on return it holds that of A' = A + sign V V^T, V n x k (column-major, ld ldv,
+ * k << n), in 2 k n^2 flops and one pass over the upper triangle per 16 columns of V instead of n^3 / 3.  In place; the strictly lower
+ * triangle of R (also inside diagonal tiles) is neither read nor written, V is not written, rows >= n of R and V are not touched.
+ * sign other than +1 / -1, negative n or k -> CAP_ERR_ARG; with n > 0 and k > 0: NULL R, V or work, ldr < n, ldv < n -> CAP_ERR_ARG;
+ * then uplo = LOWER -> CAP_ERR_UNSUPPORTED; n == 0 or k == 0 -> CAP_OK, nothing touched.  Any ldr >= n, any 8-byte aligned pointers.
+ * Asynchronous on `stream`, no host synchronisation.  `work`: device scratch >= cap_dcholupdate_work_size(n, k) doubles.
+ * The sweep (csrc/cholupdate.hip) applies one reflection per row to (R_rr; V^T[:, r]): a Householder reflection for the update, a
+ * hyperbolic one in its mixed form for the downdate.  k > 16 is taken as consecutive passes of at most 16 columns of V, each a complete
+ * update of its own.  Each pass is one launch whose workgroups claim the diagonal and tile items of the 64-blocked sweep from a ticket
+ * counter, followed by a recovery launch that finishes the pass on one workgroup if a workgroup gave up waiting (counted by
+ * cap_update_fallbacks); fixed summation order: two calls give the same bits.
+ * `info` (device int, may be NULL) is set to 0 at the start of the device work, then holds the 1-based row at which A - V V^T was found
+ * not positive definite (first one wins); the sweep carries on with NaN.  After info != 0, R IS NOT A FACTOR OF ANYTHING - keep a copy
+ * if a failing downdate must be survivable.
+ * Accuracy: the update is backward stable.  The downdate's error grows as A' approaches singularity relative to A (that is inherent:
+ * R' then depends ill-conditionedly on R and V): backward error |R'^T R' - A'|_F / |A'|_F about 5e-16 when cond(A') stays below 10,
+ * 4e-12 (CPU model of the same sweep) when a downdate lowers the condition number from 1e5 to about 5.                               */
+int cap_dcholupdate(int uplo, int sign, int64_t n, int64_t k, double* R, int64_t ldr, const double* V, int64_t ldv, int* info,
+                    double* work, void* stream);
+int64_t cap_dcholupdate_work_size(int64_t n, int64_t k);
+
 /* Z[n x nrhs] = Q^T B for a tall-skinny Q (m x n, m >> n) and a few right-hand sides B (m x nrhs), all column-major in device memory
  * (not in the reference: the expensive step of a least-squares solve on a QR factorization, cap_cacqr_solve below).  Z is overwritten,
  * its padding rows (ldz > n) are not touched; Z must not overlap Q, B or work.
@@ -373,6 +395,15 @@ int cap_cholinv_inverse(cap_cholinv_plan* plan, double* out, int64_t ld, int fil
 /* log det A = 2 sum log R_ii of the last factor call, written to ONE double in device memory; asynchronous, deterministic (fixed
  * summation order: two calls give the same bits).  NaN if the last factor failed.  Same UNSUPPORTED / ARG rules.                 */
 int cap_cholinv_logdet(cap_cholinv_plan* plan, double* logdet_dev, void* stream);
+/* The plan's resident R of the LAST factor call becomes the factor of A + sign V V^T (cap_dcholupdate's sweep, V n x k device memory,
+ * not written; sign = +1 / -1).  The next solve / inverse rebuild what they cache per factor; logdet reads the new R.  Asynchronous on
+ * `stream`, no host synchronisation; scratch lives in the plan (allocated on first use).  Single-GPU plans with complete_inv = -1 only:
+ * complete_inv = 0 / 1 hold a resident R^-1 that would go stale, multi-rank plans and "cyclic_c" -> CAP_ERR_UNSUPPORTED.  NULL plan,
+ * never factored, sign other than +1 / -1, k < 0, NULL V or ldv < n (k > 0) -> CAP_ERR_ARG; k == 0 -> CAP_OK.  A failing downdate
+ * writes its row into the plan's report: cap_cholinv_info returns it and solve / inverse / logdet give NaN, until the next factor call.
+ * If that report is already nonzero when the update runs, R and the report are left alone (decided on the device).
+ * Option "chud_kernel": 1 = one launch per pass of 16 columns (default), 0 = two launches per 64-row block step; identical bits.        */
+int cap_cholinv_update(cap_cholinv_plan* plan, int sign, const double* V, int64_t ldv, int64_t k, void* stream);
 /* host-readable status of the last factor: 0, or 1-based index of the failing pivot.  A launch of the one-launch
  * diagonal-block chain (option "chain_coop") whose workgroups were never all resident gives up after ~3 s of polling, and the
  * recovery launch behind it restores that diagonal block and re-runs it on two workgroups (counted in option
@@ -408,6 +439,11 @@ int cap_chain_inject_timeouts(int count);
  * the current device give up at their first wait.                                                                                  */
 int64_t cap_solve_fallbacks(void);
 int cap_solve_inject_timeouts(int count);
+/* And for the one-launch passes of cap_dcholupdate / cap_cholinv_update: passes of this process that the recovery launch finished on the
+ * current device (synchronises the device); TEST HOOK - the next `count` one-launch passes on the current device give up before their
+ * first item (through the normal give-up path; the result is the same bits).                                                          */
+int64_t cap_update_fallbacks(void);
+int cap_update_inject_timeouts(int count);
 /* Live measurement of the dominant kernel (trailing-update DSYRK) of the LAST factor call, enabled
  * with cap_cholinv_set_option(plan, "profile", 1): number of launches, their summed duration in ms
  * (HIP events recorded on the stream each launch went to) and summed algorithmic flops
