@@ -38,6 +38,8 @@ SIGNATURES = {
     "cap_dpotri_work_size": (i64, [i64]),
     "cap_dcholupdate": (cint, [cint, cint, i64, i64, ptr, i64, ptr, i64, ptr, ptr, ptr]),
     "cap_dcholupdate_work_size": (i64, [i64, i64]),
+    "cap_dpstrf": (cint, [cint, i64, i64, dbl, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr]),
+    "cap_dpstrf_work_size": (i64, [i64, i64]),
     "cap_dgemm_tall_tn_work_size": (i64, [i64, i64, i64]),
     "cap_dgemm_tall_tn": (cint, [i64, i64, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr]),
     "cap_desc_create": (cint, [C.POINTER(ptr), i64, i64, i64, i64]),

@@ -6,6 +6,7 @@
     X = cholinv.solve(B, pack)                                      # A X = B with the factor of the last factor call
     Ainv = cholinv.inverse(pack); ld = cholinv.logdet(pack)         # A^-1 = R^-1 R^-T and log det A = 2 sum log r_ii of that factor
     cholinv.update(V, pack); cholinv.downdate(V, pack)              # the resident factor follows A + V V^T / A - V V^T (V: n x k, k << n)
+    f = cholinv.factor_pivoted(A, max_rank, tol)                    # semidefinite / low-rank A: A[piv][:, piv] ~ R^T R, f.rank (no plan)
 
 `info` keeps upstream's four user knobs.  complete_inv = -1 is the documented extension:
 blocked right-looking Cholesky (real TRSM/SYRK, no explicit inverse) - the headline
@@ -201,3 +202,49 @@ def update(V, args, sign=+1):
 def downdate(V, args):
     """`update` with sign = -1: the factor of A - V V^T."""
     update(V, args, sign=-1)
+
+
+class pivoted_factor:
+    """What `factor_pivoted` returns: R (a `matrix` of max_rank rows by n columns, None when max_rank = 0) and piv (int64 device tensor:
+    the pivots in order, then the unselected indices in increasing order) with A[piv][:, piv] ~ R^T R.  rank, info (0: stopped at a
+    pivot <= tol, 1: max_rank steps done with the remainder above tol, 2: a NaN on the remaining diagonal) and residual_trace
+    (trace(A - R^T R)) are read from the device on first use, which synchronises."""
+
+    def __init__(self, R, piv, out):
+        self.R, self.piv, self._out, self._host = R, piv, out, None
+
+    def _read(self):
+        if self._host is None:
+            rank, resid, info = self._out
+            self._host = (int(rank.item()), int(info.item()), float(resid.item()))
+        return self._host
+
+    rank = property(lambda self: self._read()[0])
+    info = property(lambda self: self._read()[1])
+    residual_trace = property(lambda self: self._read()[2])
+
+
+def factor_pivoted(A, max_rank=None, tol=-1.0):
+    """Pivoted Cholesky (LAPACK's dpstrf with a rank cap, cap_dpstrf) of the symmetric positive semidefinite `matrix` A, whose upper
+    triangle is read and which is not written: at most max_rank (None: n) left-looking steps, stopping at the first pivot <= tol
+    (tol < 0: n eps max_i a_ii; otherwise absolute).  O(n rank^2) work, no plan.  Asynchronous on the current stream until rank, info
+    or residual_trace of the returned `pivoted_factor` is read."""
+    n = A.num_rows_global()
+    if n != A.num_columns_global():
+        raise _lib.CapitalError("factor_pivoted needs a square matrix")
+    max_rank = n if max_rank is None else int(max_rank)
+    if not 0 <= max_rank <= n:
+        raise _lib.CapitalError("max_rank must be in [0, n]")
+    L = _lib.lib()
+    R = matrix(n, max_rank, 1, 1, rect, device=A.device) if max_rank > 0 else None
+    piv = torch.empty(n, dtype=torch.int64, device=A.device)
+    rank = torch.zeros(1, dtype=torch.int64, device=A.device)
+    info = torch.zeros(1, dtype=torch.int32, device=A.device)
+    resid = torch.zeros(1, dtype=torch.float64, device=A.device)
+    work = torch.empty(max(int(L.cap_dpstrf_work_size(n, max_rank)), 2), dtype=torch.float64, device=A.device)
+    _lib.check(L.cap_dpstrf(1, n, max_rank, float(tol), A.data_ptr(), A.ld(), R.data_ptr() if R is not None else None,
+                            R.ld() if R is not None else 1, piv.data_ptr(), rank.data_ptr(), resid.data_ptr(), info.data_ptr(),
+                            work.data_ptr(), cur_stream()), "cholinv::factor_pivoted")
+    out = pivoted_factor(R, piv, (rank, resid, info))
+    out._work = work            # stays alive until the stream has used it (the caching allocator is stream-ordered; this is the belt)
+    return out

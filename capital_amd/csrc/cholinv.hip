@@ -1664,6 +1664,20 @@ int cap_cholinv_update(cap_cholinv_plan* p, int sign, const double* V, int64_t l
   return cap_chud_run(sign, n, k, p->R, p->ldr, V, ldv, p->info_dev, 1, p->ud_work, p->chud_kernel, cap_stream(stream));
 }
 
+// ---- pivoted Cholesky (LAPACK's dpstrf with a rank cap): A[piv][:, piv] ~ R^T R for a semidefinite / numerically rank-deficient A, its
+// numerical rank and the trace of what is left, by the left-looking steps of pstrf.hip: O(n rank^2), A only read
+int64_t cap_dpstrf_work_size(int64_t n, int64_t max_rank) { return cap_pstrf_work_size(n, max_rank); }
+
+int cap_dpstrf(int uplo, int64_t n, int64_t max_rank, double tol, const double* A, int64_t lda, double* R, int64_t ldr, int64_t* piv,
+               int64_t* rank, double* resid, int* info, double* work, void* stream) {
+  if (n < 0 || max_rank < 0 || max_rank > n || tol != tol) return CAP_ERR_ARG;
+  if (n > 0 && (!A || !piv || !rank || !work || lda < n)) return CAP_ERR_ARG;
+  if (n > 0 && max_rank > 0 && (!R || ldr < max_rank)) return CAP_ERR_ARG;
+  if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrf
+  if (n == 0) return CAP_OK;
+  return cap_pstrf_run(n, max_rank, tol, A, lda, R, ldr, piv, rank, resid, info, work, cap_stream(stream));
+}
+
 // B = alpha op(T) B  or  alpha B op(T)  (blas::engine::_trmm, blas/interface.hpp:61-79): the upper triangle is copied
 // into a zero-filled square (BLAS does not reference the other triangle, the MFMA kernel reads full tiles), then ONE
 // out-of-place GEMM whose K ranges stop at the triangle (tags 8 / 16 / 32: half the flops of a full product).

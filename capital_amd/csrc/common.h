@@ -194,6 +194,11 @@ int cap_potrs_nan_fill(double* X, int64_t ldx, int64_t n, int64_t nrhs, const in
 int64_t cap_chud_work_size(int64_t n, int64_t k);
 int cap_chud_run(int sign, int64_t n, int64_t k, double* R, int64_t ldr, const double* V, int64_t ldv, int* info, int info_mode,
                  double* work, int one, hipStream_t s);
+// pstrf.hip: pivoted Cholesky of the symmetric A (upper triangle read, never written) in at most max_rank left-looking steps, one launch
+// per step + one in front and one behind; R (max_rank x n), piv (n), rank, resid (may be NULL), info (may be NULL) are device memory
+int64_t cap_pstrf_work_size(int64_t n, int64_t max_rank);
+int cap_pstrf_run(int64_t n, int64_t max_rank, double tol, const double* A, int64_t lda, double* R, int64_t ldr, int64_t* piv,
+                  int64_t* rank, double* resid, int* info, double* work, hipStream_t s);
 // lauum.hip: upper triangle of C = W W^T, W upper triangular (its strictly lower triangle is never used, C's never written; any n, leading
 // dimension and alignment; W and C must not overlap); the strictly lower triangle of X from its upper one; NaN over the n x n window
 // (tri = 1: its upper triangle) when *info != 0; 2 sum log R_ii into ONE device double (NaN when info != NULL and *info != 0)

@@ -1,7 +1,7 @@
 """lapack::engine mirror (reference src/lapack/engine.h:23-102, src/lapack/interface.h:49-59).
 
-_potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor) and _cholupdate (that factor after A +- V V^T) have no
-counterpart upstream.
+_potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor), _cholupdate (that factor after A +- V V^T) and _pstrf (the
+pivoted factorization of a semidefinite A, LAPACK's dpstrf) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -35,6 +35,7 @@ class Method(enum.IntEnum):
     AlapackPotrs = 0x2          # extension: not in the reference's enum
     AlapackPotri = 0x3          # extension: not in the reference's enum
     AlapackCholupdate = 0x4     # extension: not in the reference's enum
+    AlapackPstrf = 0x5          # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
 
@@ -60,6 +61,12 @@ class ArgPack_potri:
 class ArgPack_cholupdate:
     def __init__(self, order, uplo):
         self.method = Method.AlapackCholupdate
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_pstrf:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPstrf
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -114,6 +121,27 @@ class engine:
                                cur_stream(stream))
         _lib.check(st, "lapack::engine::_cholupdate")
         return int(info.item())
+
+    @staticmethod
+    def _pstrf(matrixA, matrixR, piv, n, max_rank, lda, ldr, tol, srcPackage, stream=None):
+        """Pivoted Cholesky of the symmetric positive semidefinite A (n x n, ld lda; its upper triangle is read, nothing of it written) in at
+        most max_rank steps: A[piv][:, piv] ~ R^T R with R max_rank x n (ld ldr) and piv an int64 device tensor of n entries (the pivots in
+        order, then the unselected indices).  tol < 0: n eps max_i a_ii, otherwise absolute.  Returns (rank, info, resid) - info 0: stopped
+        at a pivot <= tol, 1: max_rank steps done with the remainder above tol, 2: a NaN on the remaining diagonal; resid = trace(A - R^T R).
+        Reading them back SYNCHRONISES the stream."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        if not isinstance(piv, torch.Tensor) or not piv.is_cuda or piv.dtype != torch.int64 or piv.numel() < n or not piv.is_contiguous():
+            raise _lib.CapitalError("piv must be a contiguous int64 device tensor of n entries")
+        L = _lib.lib()
+        work = scratch(L.cap_dpstrf_work_size(n, max_rank), matrixA)
+        rank = torch.zeros(1, dtype=torch.int64, device=work.device)
+        info = torch.zeros(1, dtype=torch.int32, device=work.device)
+        resid = torch.zeros(1, dtype=torch.float64, device=work.device)
+        st = L.cap_dpstrf(int(srcPackage.uplo), n, max_rank, float(tol), dptr(matrixA), lda, dptr(matrixR), ldr, piv.data_ptr(),
+                          rank.data_ptr(), resid.data_ptr(), info.data_ptr(), dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_pstrf")
+        return int(rank.item()), int(info.item()), float(resid.item())
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

@@ -138,6 +138,33 @@ int cap_dcholupdate(int uplo, int sign, int64_t n, int64_t k, double* R, int64_t
                     double* work, void* stream);
 int64_t cap_dcholupdate_work_size(int64_t n, int64_t k);
 
+/* Pivoted Cholesky factorization with a rank cap (LAPACK's dpstrf, out of place and truncated; not in the reference): for a symmetric
+ * positive SEMIdefinite or numerically rank-deficient A (kernel / Gram / covariance matrices) it gives the numerical rank, a factor that
+ * survives a zero pivot and the low-rank approximation A[piv][:, piv] ~ R^T R in O(n rank^2) work.  A is n x n column-major (ld lda);
+ * only its upper triangle is read (the strictly lower one may hold anything), A is never written.
+ * The steps keep d, the remaining diagonal (initially diag A).  Step j = 0, 1, ...: p = the unselected index of largest d (ties: the
+ * lowest index).  A NaN among the unselected d: stop, info = 2.  d[p] <= tol_used, or j = n: stop, info = 0.  j = max_rank: stop,
+ * info = 1 (the cap was hit with the remainder still above the tolerance).  Otherwise row j of the factor is
+ * (A(p, c) - sum_{i<j} W[i, p] W[i, c]) / sqrt(d[p]) for the unselected c != p, sqrt(d[p]) itself at c = p and 0 at the columns
+ * selected before; d[c] -= W[j, c]^2; p becomes selected.  tol < 0: tol_used = n eps max_i a_ii with eps = 2^-53 (LAPACK's default);
+ * tol >= 0 is absolute, as in LAPACK.
+ * Results, all device memory: *rank = the number of steps done; piv[n] (0-based) = the chosen pivots in order, then the unselected
+ * indices in increasing order - always a permutation; R (max_rank x n, ld ldr >= max(max_rank, 1)), R[:, k] = W[:, piv[k]]: R[0:rank,
+ * 0:rank] is upper triangular with a positive, non-increasing diagonal, rows rank .. max_rank - 1 are zero, rows >= max_rank (padding)
+ * are not touched; *resid (may be NULL) = the sum of the unselected d in index order = trace(A - R^T R), the nuclear-norm error of the
+ * approximation for a semidefinite A; *info (may be NULL) as above.  info = 2 is a result, not an error: the call returns CAP_OK.
+ * Negative n, max_rank < 0 or > n, a NaN tol -> CAP_ERR_ARG; with n > 0: NULL A, piv, rank or work, lda < n -> CAP_ERR_ARG; with n > 0
+ * and max_rank > 0: NULL R or ldr < max_rank -> CAP_ERR_ARG; then uplo = LOWER -> CAP_ERR_UNSUPPORTED; n == 0 -> CAP_OK, nothing
+ * touched.  max_rank = 0 is legal: rank 0, the identity piv, resid = trace A, info = 0 if max_i a_ii <= tol_used, else 1.
+ * Asynchronous on `stream`, no host synchronisation: one launch per possible step (max_rank of them - after the stopping decision the
+ * remaining ones return at once) plus one in front and one behind (csrc/pstrf.hip).  Every summation order is fixed: two calls give
+ * the same bits.  `work`: device scratch >= cap_dpstrf_work_size(n, max_rank) doubles (>= max_rank n: the factor in natural column
+ * order; monotone in both arguments), any 8-byte aligned pointers.
+ * Accuracy: on the selected rows |A - R^T R| <= gamma_{rank+2} |R|^T |R| componentwise (the Cholesky backward-error bound).            */
+int cap_dpstrf(int uplo, int64_t n, int64_t max_rank, double tol, const double* A, int64_t lda, double* R, int64_t ldr, int64_t* piv,
+               int64_t* rank, double* resid, int* info, double* work, void* stream);
+int64_t cap_dpstrf_work_size(int64_t n, int64_t max_rank);
+
 /* Z[n x nrhs] = Q^T B for a tall-skinny Q (m x n, m >> n) and a few right-hand sides B (m x nrhs), all column-major in device memory
  * (not in the reference: the expensive step of a least-squares solve on a QR factorization, cap_cacqr_solve below).  Z is overwritten,
  * its padding rows (ldz > n) are not touched; Z must not overlap Q, B or work.
