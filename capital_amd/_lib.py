@@ -40,6 +40,15 @@ SIGNATURES = {
     "cap_dcholupdate_work_size": (i64, [i64, i64]),
     "cap_dpstrf": (cint, [cint, i64, i64, dbl, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr, ptr, ptr]),
     "cap_dpstrf_work_size": (i64, [i64, i64]),
+    "cap_dsymm_thin": (cint, [cint, cint, i64, i64, dbl, ptr, i64, ptr, i64, dbl, ptr, i64, ptr, i64, ptr, ptr]),
+    "cap_dsymm_thin_work_size": (i64, [i64, i64]),
+    "cap_dlansy": (cint, [cint, cint, i64, ptr, i64, ptr, ptr, ptr]),
+    "cap_dlansy_work_size": (i64, [i64]),
+    "cap_dpocon": (cint, [cint, i64, ptr, i64, ptr, ptr, ptr, ptr]),
+    "cap_dpocon_work_size": (i64, [i64]),
+    "cap_pocon_last_solves": (i64, []),
+    "cap_dpoerr": (cint, [cint, i64, i64, ptr, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr, ptr, ptr]),
+    "cap_dpoerr_work_size": (i64, [i64, i64]),
     "cap_dgemm_tall_tn_work_size": (i64, [i64, i64, i64]),
     "cap_dgemm_tall_tn": (cint, [i64, i64, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr]),
     "cap_desc_create": (cint, [C.POINTER(ptr), i64, i64, i64, i64]),
@@ -109,6 +118,8 @@ SIGNATURES = {
     "cap_cholinv_inverse": (cint, [ptr, ptr, i64, cint, ptr]),
     "cap_cholinv_logdet": (cint, [ptr, ptr, ptr]),
     "cap_cholinv_update": (cint, [ptr, cint, ptr, i64, i64, ptr]),
+    "cap_cholinv_rcond": (cint, [ptr, ptr, i64, ptr, ptr, ptr]),
+    "cap_cholinv_error_bounds": (cint, [ptr, ptr, i64, ptr, i64, ptr, i64, i64, ptr, ptr, ptr]),
     "cap_cholinv_info": (cint, [ptr, ptr, C.POINTER(i64)]),
     "cap_cholinv_set_option": (cint, [ptr, C.c_char_p, i64]),
     "cap_cholinv_get_option": (i64, [ptr, C.c_char_p]),

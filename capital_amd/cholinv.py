@@ -7,6 +7,9 @@
     Ainv = cholinv.inverse(pack); ld = cholinv.logdet(pack)         # A^-1 = R^-1 R^-T and log det A = 2 sum log r_ii of that factor
     cholinv.update(V, pack); cholinv.downdate(V, pack)              # the resident factor follows A + V V^T / A - V V^T (V: n x k, k << n)
     f = cholinv.factor_pivoted(A, max_rank, tol)                    # semidefinite / low-rank A: A[piv][:, piv] ~ R^T R, f.rank (no plan)
+    rc = cholinv.rcond(A, pack)                                     # LAPACK dpocon: 1 / (||A||_1 est ||A^-1||_1) of that factor (a float)
+    ferr, berr = cholinv.error_bounds(A, B, X, pack)                # LAPACK dporfs' bounds per column of a computed solution X
+    a1 = cholinv.norm1(A)                                           # ||A||_1 of a symmetric A from its upper triangle (device scalar)
 
 `info` keeps upstream's four user knobs.  complete_inv = -1 is the documented extension:
 blocked right-looking Cholesky (real TRSM/SYRK, no explicit inverse) - the headline
@@ -165,6 +168,68 @@ def logdet(args):
     out = torch.empty(1, dtype=torch.float64, device=torch.device("cuda", torch.cuda.current_device()))
     _lib.check(_lib.lib().cap_cholinv_logdet(args._plan, out.data_ptr(), cur_stream()), "cholinv::logdet")
     return float(out.item())
+
+
+def norm1(A):
+    """||A||_1 = max_j sum_i |a_ij| of the symmetric `matrix` A, read from its upper triangle alone (LAPACK dlansy, cap_dlansy), as a
+    1-element fp64 device tensor.  Asynchronous on the current stream.  A NaN in the upper triangle gives NaN."""
+    n = A.num_rows_global()
+    if n != A.num_columns_global():
+        raise _lib.CapitalError("norm1 needs a square matrix")
+    L = _lib.lib()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty(1, dtype=torch.float64, device=dev)
+    work = torch.empty(max(int(L.cap_dlansy_work_size(n)), 2), dtype=torch.float64, device=dev)
+    _lib.check(L.cap_dlansy(ord('1'), 1, n, A.data_ptr(), A.ld(), out.data_ptr(), work.data_ptr(), cur_stream()), "cholinv::norm1")
+    return out
+
+
+def rcond(A_or_anorm, args):
+    """Reciprocal condition number 1 / (||A||_1 est ||A^-1||_1) of the matrix whose factor `cholinv.factor` (or `update`) left in `args`,
+    by LAPACK's dpocon estimator on the device (cap_cholinv_rcond), as a Python float; returning it to the host SYNCHRONISES the current
+    stream.  A_or_anorm: the `matrix` A itself (its upper triangle is read for the norm), or ||A||_1 as a 1-element fp64 device tensor
+    (`norm1`) or a float.  The plan does not keep A: passing the matrix or norm that matches the resident factor is the caller's business.
+    0.0 when the last factor or downdate failed (args.last_info() reports it), as LAPACK's dposvx."""
+    if args._plan is None:
+        raise _lib.CapitalError("cholinv.rcond needs a plan that cholinv.factor has filled")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    out = torch.empty(1, dtype=torch.float64, device=dev)
+    L = _lib.lib()
+    if isinstance(A_or_anorm, matrix):
+        A = A_or_anorm
+        if A.num_rows_global() != args._n or A.num_columns_global() != args._n:
+            raise _lib.CapitalError("A must be %d x %d" % (args._n, args._n))
+        st = L.cap_cholinv_rcond(args._plan, A.data_ptr(), A.ld(), None, out.data_ptr(), cur_stream())
+    else:
+        if isinstance(A_or_anorm, torch.Tensor):
+            an = A_or_anorm.reshape(-1)
+            if an.numel() != 1 or an.dtype != torch.float64 or an.device.type != "cuda":
+                raise _lib.CapitalError("the norm must be a float or a 1-element fp64 device tensor")
+        else:
+            an = torch.full((1,), float(A_or_anorm), dtype=torch.float64, device=dev)
+        st = L.cap_cholinv_rcond(args._plan, None, 0, an.data_ptr(), out.data_ptr(), cur_stream())
+    _lib.check(st, "cholinv::rcond")
+    return float(out.item())
+
+
+def error_bounds(A, B, X, args):
+    """(ferr, berr): per column of the computed solution X of A X = B the forward error bound and the componentwise backward error of
+    LAPACK's dporfs, without its refinement (cap_cholinv_error_bounds), as fp64 device tensors of nrhs entries.  A: the `matrix` whose
+    factor is in `args` (upper triangle read; the plan does not keep A - the match is the caller's business), B, X: n x nrhs matrices.
+    Asynchronous on the current stream.  NaN in both when the last factor or downdate failed."""
+    if args._plan is None:
+        raise _lib.CapitalError("cholinv.error_bounds needs a plan that cholinv.factor has filled")
+    n, nrhs = B.num_rows_global(), B.num_columns_global()
+    if n != args._n or A.num_rows_global() != n or A.num_columns_global() != n:
+        raise _lib.CapitalError("A must be %d x %d and B have %d rows" % (args._n, args._n, args._n))
+    if X.num_rows_global() != n or X.num_columns_global() != nrhs:
+        raise _lib.CapitalError("X must be %d x %d" % (n, nrhs))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    ferr = torch.empty(nrhs, dtype=torch.float64, device=dev)
+    berr = torch.empty(nrhs, dtype=torch.float64, device=dev)
+    _lib.check(_lib.lib().cap_cholinv_error_bounds(args._plan, A.data_ptr(), A.ld(), B.data_ptr(), B.ld(), X.data_ptr(), X.ld(), nrhs,
+                                                   ferr.data_ptr(), berr.data_ptr(), cur_stream()), "cholinv::error_bounds")
+    return ferr, berr
 
 
 def _thin(args, V):

@@ -198,6 +198,15 @@ int cap_copy_rect(const double* src, int64_t sld, double* dst, int64_t dld, int6
   return CAP_OK;
 }
 
+namespace { __global__ void set_double_kernel(double* out, double v) { *out = v; } }
+
+int cap_set_double(double* out, double v, hipStream_t s) {
+  cap_acc_w(out, 0, 1, 1);
+  hipLaunchKernelGGL(set_double_kernel, dim3(1), dim3(1), 0, s, out, v);
+  CAP_HIP(hipGetLastError());
+  return CAP_OK;
+}
+
 int cap_zero_rect(double* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s) {
   if (rows <= 0 || cols <= 0) return CAP_OK;
   cap_acc_w(dst, ldd, rows, cols);

@@ -405,6 +405,9 @@ struct cap_cholinv_plan {
   double* pi_inv; int64_t pi_elems, pi_ld, pi_gen;
   // update / downdate (cap_cholinv_update): its scratch, allocated on first use; chud_kernel 1: one launch per pass, 0: stepwise
   double* ud_work; int64_t ud_work_elems; int chud_kernel;
+  // condition estimate and error bounds (cap_cholinv_rcond / cap_cholinv_error_bounds): their scratch, allocated on first use;
+  // sv_prepares counts how often the block inverses were made (get option "solve_prepares")
+  double* pe_work; int64_t pe_work_elems; int64_t sv_prepares;
 };
 
 namespace {
@@ -1168,6 +1171,7 @@ int cap_cholinv_plan_destroy(cap_cholinv_plan* p) {
   if (p->sv_work) (void)hipFree(p->sv_work);
   if (p->pi_inv) (void)hipFree(p->pi_inv);
   if (p->ud_work) (void)hipFree(p->ud_work);
+  if (p->pe_work) (void)hipFree(p->pe_work);
   if (p->streams_ready) {
     cap_stream_destroy(p->s_panel);
     for (int i = 0; i < 2; i++) { (void)hipEventDestroy(p->ev_panel[i]); (void)hipEventDestroy(p->ev_update[i]); }
@@ -1274,6 +1278,7 @@ int64_t cap_cholinv_get_option(cap_cholinv_plan* p, const char* key) {
   if (k == "chain_coop") { if (p->chain_coop >= 0) return p->chain_coop; return cap_chain_coop_get(); }
   if (k == "chain_fallbacks") return cap_chain_fallbacks();
   if (k == "solve_kernel") return p->solve_kernel;
+  if (k == "solve_prepares") return p->sv_prepares;
   if (k == "chud_kernel") return p->chud_kernel;
   if (p->dist) {
     if (k == "complete_inv") return p->complete_inv;
@@ -1546,6 +1551,16 @@ static int potrs_grow(double** buf, int64_t* have, int64_t elems) {
   return CAP_OK;
 }
 
+// the inverses of R's diagonal blocks of tb rows, made once per factor (generation) and block width
+static int plan_block_inverses(cap_cholinv_plan* p, int64_t tb, hipStream_t s) {
+  if (p->sv_inv_gen == p->gen && p->sv_inv_tb == tb) return CAP_OK;
+  const int64_t n = p->n, nblk = cap_ceil_div(n, tb);
+  CAP_TRY(potrs_grow(&p->sv_inv, &p->sv_inv_elems, nblk * tb * tb + cap_trsm_prepare_work(tb)));
+  CAP_TRY(cap_trsm_prepare(p->R, p->ldr, n, tb, p->sv_inv, p->sv_inv + nblk * tb * tb, s));
+  p->sv_inv_gen = p->gen; p->sv_inv_tb = tb; p->sv_prepares++;
+  return CAP_OK;
+}
+
 int cap_cholinv_solve(cap_cholinv_plan* p, const double* B, int64_t ldb, double* X, int64_t ldx, int64_t nrhs, void* stream) {
   if (!p) return CAP_ERR_ARG;
   if (p->dist) return CAP_ERR_UNSUPPORTED;      // multi-rank plans (and the "cyclic_c" layout, which only they have)
@@ -1555,12 +1570,8 @@ int cap_cholinv_solve(cap_cholinv_plan* p, const double* B, int64_t ldb, double*
   if (nrhs == 0) return CAP_OK;
   hipStream_t s = cap_stream(stream);
   const bool one = p->solve_kernel && nrhs <= 16;
-  const int64_t tb = one ? cap_potrs_block() : cap_trsm_block(n), nblk = cap_ceil_div(n, tb);
-  if (p->sv_inv_gen != p->gen || p->sv_inv_tb != tb) {
-    CAP_TRY(potrs_grow(&p->sv_inv, &p->sv_inv_elems, nblk * tb * tb + cap_trsm_prepare_work(tb)));
-    CAP_TRY(cap_trsm_prepare(p->R, p->ldr, n, tb, p->sv_inv, p->sv_inv + nblk * tb * tb, s));
-    p->sv_inv_gen = p->gen; p->sv_inv_tb = tb;
-  }
+  const int64_t tb = one ? cap_potrs_block() : cap_trsm_block(n);
+  CAP_TRY(plan_block_inverses(p, tb, s));
   CAP_TRY(potrs_grow(&p->sv_work, &p->sv_work_elems, potrs_scratch_elems(n, nrhs, one, tb)));
   return potrs_run(p->R, p->ldr, n, p->sv_inv, tb, one, B, ldb, X, ldx, nrhs, p->sv_work, p->info_dev, s);
 }
@@ -1585,6 +1596,115 @@ int cap_dpotrs(int uplo, int64_t n, int64_t nrhs, const double* R, int64_t ldr, 
   double* Inv = work + cap_round_up(potrs_scratch_elems(n, nrhs, one, tb), 2);
   CAP_TRY(cap_trsm_prepare(R, ldr, n, tb, Inv, Inv + cap_ceil_div(n, tb) * tb * tb, s));
   return potrs_run(R, ldr, n, Inv, tb, one, B, ldb, B, ldb, nrhs, scr, nullptr, s);
+}
+
+// ---- POCON / the bounds of PORFS: the reciprocal condition number and the backward / forward error bounds of a computed solution, from
+// the thin symmetric product of symv.hip and the device-side dlacn2 of pocon.hip
+// work of cap_dpocon: [block inverses][their TRTRI scratch][estimator]
+int64_t cap_dpocon_work_size(int64_t n) {
+  if (n <= 0) return 0;
+  const int64_t tb = cap_potrs_block();
+  return cap_ceil_div(n, tb) * tb * tb + cap_round_up(cap_trsm_prepare_work(tb), 2) + cap_pocon_est_work(n, 1) + 2;
+}
+
+int cap_dpocon(int uplo, int64_t n, const double* R, int64_t ldr, const double* anorm_dev, double* rcond_dev, double* work, void* stream) {
+  if (n < 0 || !rcond_dev || (n > 0 && (!R || !anorm_dev || !work || ldr < n))) return CAP_ERR_ARG;
+  if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpstrf
+  hipStream_t s = cap_stream(stream);
+  if (n == 0) return cap_set_double(rcond_dev, 1.0, s);
+  const int64_t tb = cap_potrs_block(), ninv = cap_ceil_div(n, tb) * tb * tb;
+  double* Inv = work; double* est = work + ninv + cap_round_up(cap_trsm_prepare_work(tb), 2);
+  CAP_TRY(cap_trsm_prepare(R, ldr, n, tb, Inv, Inv + ninv, s));
+  return cap_pocon_run(n, 1, R, ldr, Inv, nullptr, nullptr, nullptr, 0, anorm_dev, rcond_dev, nullptr, 1, nullptr, est, s);
+}
+
+// the part of the bounds that is shared by cap_dpoerr and the plan: per chunk of 16 columns the residual and |A||X| + |B| (two passes over
+// A's upper triangle), then the estimator.  scr: [thin product's parts][Res][Den][estimator]
+static int64_t poerr_scratch_elems(int64_t n, int64_t nrhs) {
+  const int64_t nc = std::min<int64_t>(nrhs, 16);
+  return cap_round_up(cap_dsymm_thin_work_size(n, nc), 2) + 2 * cap_pocon_ld(n) * nc + cap_pocon_est_work(n, nc);
+}
+static int poerr_run(int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* R, int64_t ldr, const double* Inv, const double* B,
+                     int64_t ldb, const double* X, int64_t ldx, double* ferr, double* berr, const int* info, double* scr, void* stream) {
+  hipStream_t s = cap_stream(stream);
+  const int64_t ncm = std::min<int64_t>(nrhs, 16), ldv = cap_pocon_ld(n);
+  double* sw = scr; double* Res = scr + cap_round_up(cap_dsymm_thin_work_size(n, ncm), 2);
+  double* Den = Res + ldv * ncm; double* est = Den + ldv * ncm;
+  for (int64_t c = 0; c < nrhs; c += 16) {
+    const int64_t nc = std::min<int64_t>(16, nrhs - c);
+    CAP_TRY(cap_dsymm_thin(CAP_UPPER, 0, n, nc, -1.0, A, lda, X + c * ldx, ldx, 1.0, B + c * ldb, ldb, Res, ldv, sw, stream));
+    CAP_TRY(cap_dsymm_thin(CAP_UPPER, 1, n, nc, 1.0, A, lda, X + c * ldx, ldx, 1.0, B + c * ldb, ldb, Den, ldv, sw, stream));
+    CAP_TRY(cap_pocon_run(n, nc, R, ldr, Inv, Res, Den, X + c * ldx, ldx, nullptr, ferr ? ferr + c : nullptr, berr ? berr + c : nullptr,
+                          ferr ? 1 : 0, info, est, s));
+  }
+  return CAP_OK;
+}
+
+int64_t cap_dpoerr_work_size(int64_t n, int64_t nrhs) {
+  if (n <= 0 || nrhs <= 0) return 0;
+  const int64_t tb = cap_potrs_block();
+  return cap_ceil_div(n, tb) * tb * tb + cap_round_up(cap_trsm_prepare_work(tb), 2) + poerr_scratch_elems(n, nrhs) + 2;
+}
+
+static __global__ void poerr_fill_kernel(double* a, double* b, int64_t count, double v) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < count) { if (a) a[i] = v; if (b) b[i] = v; }
+}
+static int poerr_fill(double* a, double* b, int64_t count, double v, hipStream_t s) {
+  if (count <= 0 || (!a && !b)) return CAP_OK;
+  if (cap_acc_on()) { if (a) cap_acc_w(a, 0, count, 1); if (b) cap_acc_w(b, 0, count, 1); }
+  hipLaunchKernelGGL(poerr_fill_kernel, dim3((unsigned)cap_ceil_div(count, 256)), dim3(256), 0, s, a, b, count, v);
+  CAP_HIP(hipGetLastError());
+  return CAP_OK;
+}
+
+int cap_dpoerr(int uplo, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* R, int64_t ldr, const double* B, int64_t ldb,
+               const double* X, int64_t ldx, double* ferr_dev, double* berr_dev, double* work, void* stream) {
+  if (n < 0 || nrhs < 0) return CAP_ERR_ARG;
+  if (n > 0 && nrhs > 0 && (!A || !R || !B || !X || !work || lda < n || ldr < n || ldb < n || ldx < n)) return CAP_ERR_ARG;
+  if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpstrf
+  if (nrhs == 0 || (!ferr_dev && !berr_dev)) return CAP_OK;
+  hipStream_t s = cap_stream(stream);
+  if (n == 0) return poerr_fill(ferr_dev, berr_dev, nrhs, 0.0, s);       // LAPACK: both bounds are 0 for an empty system
+  const int64_t tb = cap_potrs_block(), ninv = cap_ceil_div(n, tb) * tb * tb;
+  double* Inv = work; double* scr = work + ninv + cap_round_up(cap_trsm_prepare_work(tb), 2);
+  if (ferr_dev) CAP_TRY(cap_trsm_prepare(R, ldr, n, tb, Inv, Inv + ninv, s));
+  return poerr_run(n, nrhs, A, lda, R, ldr, Inv, B, ldb, X, ldx, ferr_dev, berr_dev, nullptr, scr, stream);
+}
+
+int cap_cholinv_rcond(cap_cholinv_plan* p, const double* A, int64_t lda, const double* anorm_dev, double* rcond_dev, void* stream) {
+  if (!p || !rcond_dev) return CAP_ERR_ARG;
+  if (p->dist) return CAP_ERR_UNSUPPORTED;      // multi-rank plans (and the "cyclic_c" layout, which only they have)
+  const int64_t n = p->n;
+  if ((A != nullptr) == (anorm_dev != nullptr) || (A && lda < n)) return CAP_ERR_ARG;
+  if (p->gen == 0) return CAP_ERR_ARG;          // no factor
+  hipStream_t s = cap_stream(stream);
+  if (n == 0) return cap_set_double(rcond_dev, 1.0, s);
+  const int64_t lw = cap_round_up(cap_dlansy_work_size(n), 2);
+  CAP_TRY(plan_block_inverses(p, cap_potrs_block(), s));
+  CAP_TRY(potrs_grow(&p->pe_work, &p->pe_work_elems, lw + 2 + cap_pocon_est_work(n, 1)));     // (error_bounds grows it for its own columns)
+  const double* an = anorm_dev;
+  if (A) {
+    CAP_TRY(cap_dlansy('1', CAP_UPPER, n, A, lda, p->pe_work + lw, p->pe_work, stream));
+    an = p->pe_work + lw;
+  }
+  return cap_pocon_run(n, 1, p->R, p->ldr, p->sv_inv, nullptr, nullptr, nullptr, 0, an, rcond_dev, nullptr, 1, p->info_dev,
+                       p->pe_work + lw + 2, s);
+}
+
+int cap_cholinv_error_bounds(cap_cholinv_plan* p, const double* A, int64_t lda, const double* B, int64_t ldb, const double* X, int64_t ldx,
+                             int64_t nrhs, double* ferr_dev, double* berr_dev, void* stream) {
+  if (!p) return CAP_ERR_ARG;
+  if (p->dist) return CAP_ERR_UNSUPPORTED;      // multi-rank plans (and the "cyclic_c" layout, which only they have)
+  const int64_t n = p->n;
+  if (nrhs < 0 || (nrhs > 0 && n > 0 && (!A || !B || !X || lda < n || ldb < n || ldx < n))) return CAP_ERR_ARG;
+  if (p->gen == 0) return CAP_ERR_ARG;          // no factor
+  if (nrhs == 0 || (!ferr_dev && !berr_dev)) return CAP_OK;
+  hipStream_t s = cap_stream(stream);
+  if (n == 0) return poerr_fill(ferr_dev, berr_dev, nrhs, 0.0, s);
+  if (ferr_dev) CAP_TRY(plan_block_inverses(p, cap_potrs_block(), s));
+  CAP_TRY(potrs_grow(&p->pe_work, &p->pe_work_elems, poerr_scratch_elems(n, nrhs)));
+  return poerr_run(n, nrhs, A, lda, p->R, p->ldr, p->sv_inv, B, ldb, X, ldx, ferr_dev, berr_dev, p->info_dev, p->pe_work, stream);
 }
 
 // ---- POTRI: A^-1 = R^-1 R^-T, the triangular inverse followed by the triangular product of lauum.hip (LAPACK's dtrtri + dlauum); log det A

@@ -120,6 +120,7 @@ int cap_leaf_trtri(const double* R, int64_t ldr, double* Rinv, int64_t ldi, int 
 // aux.hip
 int cap_copy_rect(const double* src, int64_t lds_, double* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s);
 int cap_zero_rect(double* dst, int64_t ldd, int64_t rows, int64_t cols, hipStream_t s);
+int cap_set_double(double* out, double v, hipStream_t s);   // one device double <- v
 double* cap_scratch(int64_t elems, hipStream_t stream);  // gemm.hip: per-stream device scratch (split-K partials)
 
 // gemm.hip: distributed (1 x P block-column-cyclic) trailing update with staircase mask + gathered A operand
@@ -182,11 +183,13 @@ int cap_skinny_f32a_launch(int transa, int64_t m, int64_t n, int64_t k, double a
                            double beta, double* C, int64_t ldc, hipStream_t stream);
 // potrs.hip: one substitution of the fp64 solve in one launch + its recovery launch (fwd = 1: R^T Out = In, 0: R Out = In; nrhs <= 16;
 // Inv = the inverses of R's diagonal blocks of cap_potrs_block() rows; ctr: cap_potrs_ctr_ints(n) ints the caller zeroed on `s`;
-// info != NULL and != 0: Out is NaN); the NaN fill of the blocked path
+// info != NULL and != 0: Out is NaN; skip != NULL and *skip != 0 on the device: both launches return at once and touch nothing - the word
+// belongs to a launch in front on the same stream, pocon.hip); the NaN fill of the blocked path; the device's diagnostic words
 int64_t cap_potrs_block();
 int64_t cap_potrs_ctr_ints(int64_t n);
 int cap_potrs_subst(int fwd, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* Inv, const double* In, int64_t ldin,
-                    double* Out, int64_t ldout, double* S, int64_t lds, int* ctr, const int* info, hipStream_t s);
+                    double* Out, int64_t ldout, double* S, int64_t lds, int* ctr, const int* info, hipStream_t s, const int* skip = nullptr);
+int cap_potrs_words(int** w);
 int cap_potrs_nan_fill(double* X, int64_t ldx, int64_t n, int64_t nrhs, const int* info, hipStream_t s);
 // cholupdate.hip: R'^T R' = R^T R + sign V V^T in place on the upper factor (k columns in passes of 16; one = 1: one launch per pass +
 // its recovery launch, 0: two launches per block row, same bits).  info_mode 0: `info` (may be NULL) is zeroed, then takes the first
@@ -199,6 +202,15 @@ int cap_chud_run(int sign, int64_t n, int64_t k, double* R, int64_t ldr, const d
 int64_t cap_pstrf_work_size(int64_t n, int64_t max_rank);
 int cap_pstrf_run(int64_t n, int64_t max_rank, double tol, const double* A, int64_t lda, double* R, int64_t ldr, int64_t* piv,
                   int64_t* rank, double* resid, int* info, double* work, hipStream_t s);
+// pocon.hip: LAPACK's dlacn2 for diag(w) A^-1 and its transpose, nc <= 16 columns in lock-step (w = W[:, c], W == NULL: ones), A = R^T R with
+// Inv the inverses of R's diagonal blocks of cap_potrs_block() rows.  In front: the start vectors and, when Res != NULL, the dporfs quantities
+// of the columns - berr (may be NULL) from Res = B - A X and Den = |A||X| + |B| (n x nc, leading dimension ldv = cap_pocon_ld(n); Den is
+// overwritten by w), max |x| from X.  Behind: anorm != NULL: *out = 1 / (anorm est) (cap_dpocon's edge cases), else out[c] = est_c / max |x_c|.
+// info != NULL and *info != 0: out = 0 with anorm, NaN without, berr NaN, no solves.  want_est = 0: only the part in front.
+int64_t cap_pocon_ld(int64_t n);
+int64_t cap_pocon_est_work(int64_t n, int64_t nc);
+int cap_pocon_run(int64_t n, int64_t nc, const double* R, int64_t ldr, const double* Inv, const double* Res, double* Den, const double* X,
+                  int64_t ldx, const double* anorm, double* out, double* berr, int want_est, const int* info, double* work, hipStream_t s);
 // lauum.hip: upper triangle of C = W W^T, W upper triangular (its strictly lower triangle is never used, C's never written; any n, leading
 // dimension and alignment; W and C must not overlap); the strictly lower triangle of X from its upper one; NaN over the n x n window
 // (tri = 1: its upper triangle) when *info != 0; 2 sum log R_ii into ONE device double (NaN when info != NULL and *info != 0)

@@ -40,8 +40,10 @@ struct PotrsArgs {
   double* Out; int64_t ldout;         // solution of this substitution
   double* S; int64_t lds;             // partial sums, block b at rows b PT
   int* ctr;                           // [0] ticket, [1] state (1 = a workgroup gave up), [2, 2 + nb) published D_j, [2 + nb, 2 + 2 nb) parts in S_i
-  int* words;                         // device-wide: [0] substitutions finished by the recovery launch, [1] injected give-ups pending
+  int* words;                         // device-wide: [0] substitutions finished by the recovery launch, [1] injected give-ups pending,
+                                      // [2] solves the last condition estimate took (pocon.hip)
   const int* info;                    // != 0 after the factor: the outputs are NaN
+  const int* skip;                    // optional: != 0 turns this launch and its recovery launch into immediate exits
   int n, nrhs, nb, fwd, recover;
 };
 
@@ -198,6 +200,8 @@ __global__ void __launch_bounds__(PTHREADS) potrs_subst_kernel(const PotrsArgs a
   int* sh = reinterpret_cast<int*>(V + PT * PNR_MAX);      // [0] ticket, [1] wait result
   const int t = threadIdx.x, nb = a.nb;
   int* const state = a.ctr + 1;
+  // the skip word is written by a launch in front of this one, never during it: every thread reads the same value
+  if (a.skip && *a.skip != 0) return;
   const bool nan_out = a.info && *a.info != 0;
 
   if (a.recover) {
@@ -296,13 +300,13 @@ int64_t cap_potrs_block() { return PT; }
 int64_t cap_potrs_ctr_ints(int64_t n) { return cap_round_up(2 + 2 * cap_ceil_div(n, PT), 4); }
 
 int cap_potrs_subst(int fwd, int64_t n, int64_t nrhs, const double* R, int64_t ldr, const double* Inv, const double* In, int64_t ldin,
-                    double* Out, int64_t ldout, double* S, int64_t lds, int* ctr, const int* info, hipStream_t s) {
+                    double* Out, int64_t ldout, double* S, int64_t lds, int* ctr, const int* info, hipStream_t s, const int* skip) {
   if (n <= 0 || nrhs <= 0) return CAP_OK;
   if (nrhs > PNR_MAX || n > ((int64_t)1 << 24)) return CAP_ERR_ARG;
   int* words = nullptr;
   CAP_TRY(solve_words(&words));
   const int nb = (int)cap_ceil_div(n, PT);
-  PotrsArgs g{R, ldr, Inv, In, ldin, Out, ldout, S, lds, ctr, words, info, (int)n, (int)nrhs, nb, fwd, 0};
+  PotrsArgs g{R, ldr, Inv, In, ldin, Out, ldout, S, lds, ctr, words, info, skip, (int)n, (int)nrhs, nb, fwd, 0};
   const int items = nb * (nb + 1) / 2;
   const int wgs = std::max(1, std::min(items, resident_wgs()));
   // access notes: the off-diagonal blocks of R's upper triangle, the block inverses, the input, the output and the partial sums this
@@ -317,6 +321,7 @@ int cap_potrs_subst(int fwd, int64_t n, int64_t nrhs, const double* R, int64_t l
     cap_acc_rw(ctr, 0, cap_potrs_ctr_ints(n), 1, 0, 4);
     cap_acc_atomic(words, 4, 4);
     if (info) cap_acc_r(info, 1, 1, 1, 0, 4);
+    if (skip) cap_acc_r(skip, 1, 1, 1, 0, 4);
   };
   for (int rec = 0; rec < 2; rec++) {
     g.recover = rec;
@@ -339,6 +344,8 @@ int cap_potrs_nan_fill(double* X, int64_t ldx, int64_t n, int64_t nrhs, const in
   CAP_HIP(hipGetLastError());
   return CAP_OK;
 }
+
+int cap_potrs_words(int** w) { return solve_words(w); }
 
 extern "C" int64_t cap_solve_fallbacks(void) {
   int* w = nullptr;

@@ -1,7 +1,8 @@
 """lapack::engine mirror (reference src/lapack/engine.h:23-102, src/lapack/interface.h:49-59).
 
-_potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor), _cholupdate (that factor after A +- V V^T) and _pstrf (the
-pivoted factorization of a semidefinite A, LAPACK's dpstrf) have no counterpart upstream.
+_potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor), _cholupdate (that factor after A +- V V^T), _pstrf (the
+pivoted factorization of a semidefinite A, LAPACK's dpstrf), _lansy (the 1-norm of a symmetric matrix), _pocon (the reciprocal condition
+number from the factor, LAPACK's dpocon) and _poerr (the error bounds of LAPACK's dporfs) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -36,6 +37,9 @@ class Method(enum.IntEnum):
     AlapackPotri = 0x3          # extension: not in the reference's enum
     AlapackCholupdate = 0x4     # extension: not in the reference's enum
     AlapackPstrf = 0x5          # extension: not in the reference's enum
+    AlapackLansy = 0x6          # extension: not in the reference's enum
+    AlapackPocon = 0x7          # extension: not in the reference's enum
+    AlapackPoerr = 0x8          # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
 
@@ -67,6 +71,24 @@ class ArgPack_cholupdate:
 class ArgPack_pstrf:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPstrf
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_lansy:
+    def __init__(self, order, uplo, norm='1'):
+        self.method = Method.AlapackLansy
+        self.order, self.uplo, self.norm = Order(order), UpLo(uplo), norm
+
+
+class ArgPack_pocon:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPocon
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_poerr:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPoerr
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -142,6 +164,47 @@ class engine:
                           rank.data_ptr(), resid.data_ptr(), info.data_ptr(), dptr(work), cur_stream(stream))
         _lib.check(st, "lapack::engine::_pstrf")
         return int(rank.item()), int(info.item()), float(resid.item())
+
+    @staticmethod
+    def _lansy(matrixA, n, lda, srcPackage, stream=None):
+        """||A||_1 (srcPackage.norm = '1', 'O' or 'I': equal for a symmetric matrix) of the symmetric A (n x n, ld lda), read from its upper
+        triangle alone, as a 1-element fp64 device tensor.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        work = scratch(max(L.cap_dlansy_work_size(n), 2), matrixA)
+        out = torch.zeros(1, dtype=torch.float64, device=work.device)
+        st = L.cap_dlansy(ord(srcPackage.norm), int(srcPackage.uplo), n, dptr(matrixA), lda, out.data_ptr(), dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_lansy")
+        return out
+
+    @staticmethod
+    def _pocon(matrixR, n, ldr, anorm, srcPackage, stream=None):
+        """Reciprocal condition number 1 / (anorm est ||A^-1||_1) of A = R^T R, R the upper factor _potrf left (n x n, ld ldr), anorm =
+        ||A||_1 as a 1-element fp64 device tensor (_lansy).  Returns a 1-element fp64 device tensor.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        work = scratch(max(L.cap_dpocon_work_size(n), 2), matrixR)
+        out = torch.zeros(1, dtype=torch.float64, device=work.device)
+        st = L.cap_dpocon(int(srcPackage.uplo), n, dptr(matrixR), ldr, anorm.data_ptr(), out.data_ptr(), dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_pocon")
+        return out
+
+    @staticmethod
+    def _poerr(matrixA, matrixR, matrixB, matrixX, n, nrhs, lda, ldr, ldb, ldx, srcPackage, stream=None):
+        """(ferr, berr) of LAPACK's dporfs, without its refinement, for the computed solution X (n x nrhs, ld ldx) of A X = B: A symmetric
+        (upper triangle read, ld lda), R its upper factor (ld ldr), B n x nrhs (ld ldb).  Two fp64 device tensors of nrhs entries.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        work = scratch(max(L.cap_dpoerr_work_size(n, nrhs), 2), matrixA)
+        ferr = torch.zeros(max(nrhs, 1), dtype=torch.float64, device=work.device)
+        berr = torch.zeros(max(nrhs, 1), dtype=torch.float64, device=work.device)
+        st = L.cap_dpoerr(int(srcPackage.uplo), n, nrhs, dptr(matrixA), lda, dptr(matrixR), ldr, dptr(matrixB), ldb, dptr(matrixX), ldx,
+                          ferr.data_ptr(), berr.data_ptr(), dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_poerr")
+        return ferr[:nrhs], berr[:nrhs]
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

@@ -165,6 +165,68 @@ int cap_dpstrf(int uplo, int64_t n, int64_t max_rank, double tol, const double* 
                int64_t* rank, double* resid, int* info, double* work, void* stream);
 int64_t cap_dpstrf_work_size(int64_t n, int64_t max_rank);
 
+/* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
+ * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
+ * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
+ * beta == 0 never reads B (it may be NULL; NaN in it cannot reach Y); alpha == 0 never reads A, X or work.  Y may be B (in place).  The
+ * strictly lower triangle of A is never read, inside diagonal tiles too; rows >= n of A, X, B (padding) are never read, those of Y never
+ * written.  Any lda / ldx / ldb / ldy >= n, any 8-byte aligned pointers, any nrhs >= 0: more than 16 columns are taken in chunks of 16,
+ * one pass over the triangle each.
+ * Negative n or nrhs, absolute other than 0 / 1, a NaN alpha or beta -> CAP_ERR_ARG; with n > 0 and nrhs > 0: NULL Y or ldy < n; with
+ * alpha != 0: NULL A, X or work, lda < n, ldx < n; with beta != 0: NULL B or ldb < n; the address range of Y meeting that of A, X or work
+ * (alpha != 0) -> CAP_ERR_ARG; then uplo = LOWER -> CAP_ERR_UNSUPPORTED; n == 0 or nrhs == 0 -> CAP_OK, nothing touched.
+ * Asynchronous on `stream`, no host synchronisation.  csrc/symv.hip: one workgroup per 512 x 512 super-block of the upper block triangle
+ * streams it once through LDS and uses every element for both A_IJ X_J and A_IJ^T X_I, the parts go to the super-block's own slot of
+ * `work`, a second launch adds the parts of each block row in a fixed order and applies alpha, beta and B.  No floating-point atomics:
+ * two calls give the same bits.  work >= cap_dsymm_thin_work_size(n, nrhs) doubles (0 for an empty problem, monotone in both arguments,
+ * constant beyond 16 columns).                                                                                                        */
+int cap_dsymm_thin(int uplo, int absolute, int64_t n, int64_t nrhs, double alpha, const double* A, int64_t lda, const double* X,
+                   int64_t ldx, double beta, const double* B, int64_t ldb, double* Y, int64_t ldy, double* work, void* stream);
+int64_t cap_dsymm_thin_work_size(int64_t n, int64_t nrhs);
+
+/* LAPACK dlansy for the 1-norm: *out_dev (ONE device double) = max_j sum_i |a_ij| of the symmetric A, from its upper triangle alone
+ * (the strictly lower one is never read).  norm = '1', 'O' or 'I' (equal for a symmetric matrix); any other norm -> CAP_ERR_UNSUPPORTED.
+ * It is cap_dsymm_thin's absolute product with a column of ones that the kernel supplies itself, followed by a maximum.  A NaN in the
+ * upper triangle gives NaN (as LAPACK).  Negative n, NULL out_dev; with n > 0: NULL A or work, lda < n -> CAP_ERR_ARG; then the norm and
+ * uplo = LOWER -> CAP_ERR_UNSUPPORTED; n == 0 -> *out_dev = 0.  Asynchronous, deterministic.  work >= cap_dlansy_work_size(n) doubles.   */
+int cap_dlansy(int norm, int uplo, int64_t n, const double* A, int64_t lda, double* out_dev, double* work, void* stream);
+int64_t cap_dlansy_work_size(int64_t n);
+
+/* LAPACK dpocon beside cap_dpotrf: *rcond_dev (ONE device double) = 1 / (anorm est), est = LAPACK's estimate of ||A^-1||_1 for A = R^T R,
+ * R the upper factor (the other triangle is not referenced), *anorm_dev = ||A||_1 (cap_dlansy) in device memory.  est is a LOWER
+ * bound of ||A^-1||_1, so rcond >= the true reciprocal condition number up to rounding: the estimate is optimistic, in practice by less than a
+ * factor 3 (1.0 - 1.4 on the matrices of tests/test_gpu_pocon.py).
+ * The estimator (csrc/pocon.hip) is dlacn2 exactly - start vector 1 / n, sign vectors, the stop at a repeated sign vector or an estimate
+ * that did not grow, arg max with the lowest index winning ties, at most 5 iterations, the final alternating-sign vector with its
+ * 2 |x|_1 / (3 n) floor - run on the device: its state lives in device memory, one step is one solve with R (the two substitutions of
+ * cap_dpotrs, the inverses of R's diagonal blocks made ONCE per call) and a small kernel that takes the step's decision.  No host
+ * synchronisation: the 11 solves dlacn2 can need are always enqueued, and the ones behind the last decision return at once (4 - 5 are
+ * typical).  Fixed reduction orders: two calls give the same bits.  LAPACK's overflow rescaling (dlatrs' scale) is not reproduced.
+ * n == 0 -> 1; *anorm_dev == 0 -> 0; NaN anorm -> NaN.  Negative n, NULL rcond_dev; with n > 0: NULL R, anorm_dev or work, ldr < n ->
+ * CAP_ERR_ARG; then uplo = LOWER -> CAP_ERR_UNSUPPORTED.  work >= cap_dpocon_work_size(n) doubles.
+ * cap_pocon_last_solves: DIAGNOSTIC - the number of solves the last estimate on the current device actually took, the largest over the
+ * columns of its LAST chunk of 16 (cap_dpoerr with more columns reports the last chunk only); one word per device, written with a plain
+ * store: estimates running at the same time on several streams overwrite each other's count (synchronises the device).                                                                                                  */
+int cap_dpocon(int uplo, int64_t n, const double* R, int64_t ldr, const double* anorm_dev, double* rcond_dev, double* work, void* stream);
+int64_t cap_dpocon_work_size(int64_t n);
+int64_t cap_pocon_last_solves(void);
+
+/* The bounds of LAPACK dporfs WITHOUT its refinement (an fp64 Cholesky solve already has a componentwise backward error of a few eps,
+ * which refinement does not improve): X (n x nrhs) is a computed solution of A X = B, A symmetric with its upper triangle given (the
+ * strictly lower one is never read), R its upper factor.  Per column j, device arrays of nrhs doubles, either may be NULL:
+ *   berr[j] = max_i |B - A X|_i / (|A||X| + |B|)_i, the componentwise backward error, with LAPACK's guard: where the denominator is
+ *             <= safe2 = safe1 / eps, safe1 = (n + 1) safmin is added to numerator and denominator;
+ *   ferr[j] = est || |A^-1| (|r_j| + (n + 1) eps (|A||x_j| + |b_j|)) ||_inf / ||x_j||_inf, a bound of ||x_j - x*||_inf / ||x_j||_inf, by
+ *             cap_dpocon's estimator on diag(w) A^-1, up to 16 columns in lock-step (x_j == 0: the numerator alone, as LAPACK).
+ * eps = 2^-53, safmin = 2^-1022 (dlamch).  Cost: two passes over A's upper triangle per 16 columns (cap_dsymm_thin: the residual, then
+ * the absolute product), and for ferr the estimator's solves with 16 columns each.  Nothing is written but ferr, berr and work.
+ * Negative n or nrhs; with n > 0 and nrhs > 0: NULL A, R, B, X or work, lda / ldr / ldb / ldx < n -> CAP_ERR_ARG; then uplo = LOWER ->
+ * CAP_ERR_UNSUPPORTED; nrhs == 0 -> CAP_OK; n == 0 -> both bounds 0.  Asynchronous, no host synchronisation, deterministic.
+ * work >= cap_dpoerr_work_size(n, nrhs) doubles.                                                                                      */
+int cap_dpoerr(int uplo, int64_t n, int64_t nrhs, const double* A, int64_t lda, const double* R, int64_t ldr, const double* B, int64_t ldb,
+               const double* X, int64_t ldx, double* ferr_dev, double* berr_dev, double* work, void* stream);
+int64_t cap_dpoerr_work_size(int64_t n, int64_t nrhs);
+
 /* Z[n x nrhs] = Q^T B for a tall-skinny Q (m x n, m >> n) and a few right-hand sides B (m x nrhs), all column-major in device memory
  * (not in the reference: the expensive step of a least-squares solve on a QR factorization, cap_cacqr_solve below).  Z is overwritten,
  * its padding rows (ldz > n) are not touched; Z must not overlap Q, B or work.
@@ -431,6 +493,21 @@ int cap_cholinv_logdet(cap_cholinv_plan* plan, double* logdet_dev, void* stream)
  * If that report is already nonzero when the update runs, R and the report are left alone (decided on the device).
  * Option "chud_kernel": 1 = one launch per pass of 16 columns (default), 0 = two launches per 64-row block step; identical bits.        */
 int cap_cholinv_update(cap_cholinv_plan* plan, int sign, const double* V, int64_t ldv, int64_t k, void* stream);
+/* cap_dpocon / cap_dpoerr on the plan's resident R of the LAST factor or update call (single-GPU plans, any complete_inv; multi-rank plans
+ * and "cyclic_c" -> CAP_ERR_UNSUPPORTED; never factored -> CAP_ERR_ARG, as cap_cholinv_solve).  They share the block inverses that
+ * cap_cholinv_solve keeps per factor - whichever runs first makes them - and keep their scratch in the plan (allocated on first use, sized
+ * for the call: rcond alone needs about n^2 / 512 + 5 n doubles).  The plan keeps ONE set of block inverses, of the width of the one-launch
+ * substitution (nrhs <= 16, option "solve_kernel" = 1, the default): a solve with more than 16 right-hand sides or with "solve_kernel" = 0
+ * uses another width and replaces the set, so alternating such solves with rcond / error_bounds rebuilds it each time.
+ * cap_cholinv_rcond: exactly one of A / anorm_dev is non-NULL (else CAP_ERR_ARG): the 1-norm is computed from A's upper triangle
+ * (cap_dlansy, then bit for bit cap_dpocon's result), or taken as given.  cap_cholinv_error_bounds: A, B, X as for cap_dpoerr.
+ * THE PLAN DOES NOT KEEP A: passing the matrix (or norm) that matches the resident factor - after cap_cholinv_update the updated
+ * matrix - is the caller's business.  If the last factor or downdate reported info != 0: rcond = 0 (what LAPACK's dposvx reports for a
+ * matrix that is not positive definite - `rcond < eps` stays a valid test, which NaN would not be) and ferr = berr = NaN, beside the
+ * NaN of solve / inverse / logdet.  Asynchronous on `stream`, no host synchronisation.                                                 */
+int cap_cholinv_rcond(cap_cholinv_plan* plan, const double* A, int64_t lda, const double* anorm_dev, double* rcond_dev, void* stream);
+int cap_cholinv_error_bounds(cap_cholinv_plan* plan, const double* A, int64_t lda, const double* B, int64_t ldb, const double* X,
+                             int64_t ldx, int64_t nrhs, double* ferr_dev, double* berr_dev, void* stream);
 /* host-readable status of the last factor: 0, or 1-based index of the failing pivot.  A launch of the one-launch
  * diagonal-block chain (option "chain_coop") whose workgroups were never all resident gives up after ~3 s of polling, and the
  * recovery launch behind it restores that diagonal block and re-runs it on two workgroups (counted in option
