@@ -51,6 +51,9 @@ SIGNATURES = {
     "cap_dpoerr_work_size": (i64, [i64, i64]),
     "cap_dgemm_tall_tn_work_size": (i64, [i64, i64, i64]),
     "cap_dgemm_tall_tn": (cint, [i64, i64, i64, ptr, i64, ptr, i64, ptr, i64, ptr, ptr]),
+    "cap_dgram256_work_size": (i64, [i64]),
+    "cap_dgram256": (cint, [i64, ptr, i64, ptr, i64, ptr, i64, ptr]),
+    "cap_dqrapply256": (cint, [i64, ptr, i64, ptr, ptr, i64, i64, ptr]),
     "cap_desc_create": (cint, [C.POINTER(ptr), i64, i64, i64, i64]),
     "cap_desc_create_view": (cint, [C.POINTER(ptr), i64, i64, i64, i64, ptr, i64]),
     "cap_desc_create_bc": (cint, [C.POINTER(ptr), i64, i64, i64, cint, cint, cint, cint, ptr, i64]),

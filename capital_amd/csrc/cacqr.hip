@@ -40,8 +40,8 @@ int cap_rec_cholinv_full(double* R, int64_t ldr, double* Ri, int64_t ldi, int64_
 int64_t cap_rec_work_size(int64_t n);
 // cqr_kernels.hip: the n = 256 streaming kernels (whole-Gram workgroups; persistent row-streaming Q R^-1)
 int64_t cap_gram256_work(int64_t m);
-int cap_gram256_launch(const double* Q, int64_t ld, int64_t m, double* G, int64_t ldg, double* work, hipStream_t s);
-int cap_qrapply256_launch(const double* Qin, int64_t ldin, const double* Ri, double* Qout, int64_t ldout, int64_t m, hipStream_t s);
+int cap_gram256_launch(const double* Q, int64_t ld, int64_t m, double* G, int64_t ldg, double* work, hipStream_t s, int64_t max_wgs = 0);
+int cap_qrapply256_launch(const double* Qin, int64_t ldin, const double* Ri, double* Qout, int64_t ldout, int64_t m, hipStream_t s, int64_t max_wgs = 0);
 // cqr_shift.hip: the conditioning launches of a shifted sweep
 int cap_scqr_set_rows(double* m_global, int64_t m_local, hipStream_t s);
 int cap_scqr_equilibrate(double* G, int64_t ldg, int64_t n, const double* m_global, double* d, double* shift, hipStream_t s);

@@ -308,17 +308,20 @@ __global__ void __launch_bounds__(512, 2) qrapply256_kernel(const ApplyArgs g) {
 }  // namespace
 
 // G (ldg >= 256, upper triangle written) = Q^T Q for Q m x 256 (ld), m % 16 == 0.  work: >= cap_gram256_work(m) doubles.
-int64_t cap_gram256_slabs(int64_t m) {
+// max_wgs > 0 caps the number of row slabs (kernel-level tests: several K-tile counts per workgroup at a small m); 0 = one slab per CU.
+int64_t cap_gram256_slabs(int64_t m, int64_t max_wgs = 0) {
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return std::max<int64_t>(1, std::min<int64_t>(cus, m / 512));     // at least 32 K tiles per workgroup
+  int64_t nslab = std::min<int64_t>(cus, m / 512);                  // at least 32 K tiles per workgroup
+  if (max_wgs > 0) nslab = std::min(nslab, max_wgs);
+  return std::max<int64_t>(1, nslab);
 }
 int64_t cap_gram256_work(int64_t m) { return cap_gram256_slabs(m) * GN * GN; }
 
-int cap_gram256_launch(const double* Q, int64_t ld, int64_t m, double* G, int64_t ldg, double* work, hipStream_t s) {
-  if (!Q || !G || !work || m <= 0 || (m % BK) || ld < m || ldg < GN || (ld & 1) || ((uintptr_t)Q & 15)) return CAP_ERR_UNSUPPORTED;
+int cap_gram256_launch(const double* Q, int64_t ld, int64_t m, double* G, int64_t ldg, double* work, hipStream_t s, int64_t max_wgs = 0) {
+  if (!Q || !G || !work || m <= 0 || (m % BK) || ld < m || ldg < GN || (ld & 1) || ((uintptr_t)Q & 15) || max_wgs < 0) return CAP_ERR_UNSUPPORTED;
   if (128 * ld * 8 >= 0xfffffff0LL) return CAP_ERR_UNSUPPORTED;
-  const int64_t nslab = cap_gram256_slabs(m);
+  const int64_t nslab = cap_gram256_slabs(m, max_wgs);
   GramArgs g{Q, ld, m, cap_round_up(cap_ceil_div(m, nslab), BK), work};
   cap_acc_r(Q, ld, m, GN); cap_acc_w(work, 0, nslab * GN * GN, 1);
   hipLaunchKernelGGL(gram256_kernel, dim3((unsigned)nslab), dim3(512), G_STAGES * G_TILE * sizeof(double), s, g);
@@ -328,16 +331,24 @@ int cap_gram256_launch(const double* Q, int64_t ld, int64_t m, double* G, int64_
   return CAP_OK;
 }
 
-// Qout (m x 256, ldout) = Qin (m x 256, ldin) * Ri (256 x 256 upper, ld 256, strictly-lower part zero); m % 128 == 0
-int cap_qrapply256_launch(const double* Qin, int64_t ldin, const double* Ri, double* Qout, int64_t ldout, int64_t m, hipStream_t s) {
-  if (!Qin || !Ri || !Qout || m <= 0 || (m % 128) || ldin < m || ldout < m || (ldin & 1) || ((uintptr_t)Qin & 15) || ((uintptr_t)Ri & 15))
+// Qout (m x 256, ldout) = Qin (m x 256, ldin) * Ri (256 x 256 upper, ld 256, strictly-lower part zero); m % 128 == 0.
+// max_wgs > 0 caps the grid (kernel-level tests: several row tiles per workgroup at a small m); 0 = one workgroup per CU.
+// The kernel addresses a row tile through 32-bit byte offsets behind a 64-bit base: K row kr <= 15 of Qin at kr * ldin * 8 plus a lane
+// offset < 1024 (issue_a), block-column row kg + 4 r <= 15 of Qout at (kg + 12) * ldout * 8 plus a lane offset < 1024 + 8 bytes
+// (CQY_STORE).  Both stay below the descriptors' 0xffffffff records with the margin gemm.hip's usebuf rule keeps as long as
+// 15 * ld * 8 + 1024 < 0xfffffff0.
+constexpr int64_t APPLY_LD_LIMIT = (0xfffffff0LL - 1024 - 1) / (15 * 8);     // 35791385: the largest leading dimension those offsets carry
+int cap_qrapply256_launch(const double* Qin, int64_t ldin, const double* Ri, double* Qout, int64_t ldout, int64_t m, hipStream_t s, int64_t max_wgs = 0) {
+  if (!Qin || !Ri || !Qout || m <= 0 || (m % 128) || ldin < m || ldout < m || (ldin & 1) || ((uintptr_t)Qin & 15) || ((uintptr_t)Ri & 15) || max_wgs < 0)
     return CAP_ERR_UNSUPPORTED;
+  if (ldin > APPLY_LD_LIMIT || ldout > APPLY_LD_LIMIT || m / 128 > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;
   int dev = 0, cus = 256;
   CAP_HIP(hipGetDevice(&dev));
   (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   static const int contig = CAP_ENV("CAP_CQR_CONTIG") ? atoi(CAP_ENV("CAP_CQR_CONTIG")) : 1;
   ApplyArgs g{Qin, ldin, Ri, Qout, ldout, (int)(m / 128), contig};
-  const int grid = (int)std::min<int64_t>(cus, g.ntiles);
+  int grid = (int)std::min<int64_t>(cus, g.ntiles);
+  if (max_wgs > 0) grid = (int)std::min<int64_t>(grid, max_wgs);
   // CAP_CQR_DIAG is timing surgery only (1 = no stores, 2 = no MFMA: results are wrong)
   const size_t lds = (A_NST * TA + B_NST * TB) * sizeof(double);
   const dim3 gr((unsigned)grid), bl(512);
@@ -353,3 +364,18 @@ int cap_qrapply256_launch(const double* Qin, int64_t ldin, const double* Ri, dou
   CAP_HIP(hipGetLastError());
   return CAP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ kernel-level entries (capital_amd.h)
+extern "C" {
+
+int64_t cap_dgram256_work_size(int64_t m) { return m > 0 ? cap_gram256_work(m) : 0; }
+
+int cap_dgram256(int64_t m, const double* Q, int64_t ldq, double* G, int64_t ldg, double* work, int64_t max_wgs, void* stream) {
+  return cap_gram256_launch(Q, ldq, m, G, ldg, work, (hipStream_t)stream, max_wgs);
+}
+
+int cap_dqrapply256(int64_t m, const double* Qin, int64_t ldin, const double* Ri, double* Qout, int64_t ldout, int64_t max_wgs, void* stream) {
+  return cap_qrapply256_launch(Qin, ldin, Ri, Qout, ldout, m, (hipStream_t)stream, max_wgs);
+}
+
+}  // extern "C"

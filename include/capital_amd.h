@@ -240,6 +240,31 @@ int64_t cap_dgemm_tall_tn_work_size(int64_t m, int64_t n, int64_t nrhs);
 int cap_dgemm_tall_tn(int64_t m, int64_t n, int64_t nrhs, const double* Q, int64_t ldq, const double* B, int64_t ldb, double* Z,
                       int64_t ldz, double* work, void* stream);
 
+/* The two streaming kernels of a CholeskyQR sweep at n = 256 columns (csrc/cqr_kernels.hip), on their own (not in the reference; the
+ * plan calls of cap_cacqr_factor run exactly these launches).  Kernel-level entries: whatever the kernels cannot run is refused with
+ * CAP_ERR_UNSUPPORTED before anything is launched or written - there is no other route behind them.  All operands column-major in
+ * device memory.  max_wgs = 0: one workgroup per CU as the plans launch them; max_wgs > 0 caps the grid (a test gives one workgroup
+ * several row tiles at a small m with it, whatever the device's CU count); max_wgs < 0 is refused.  Asynchronous, deterministic.
+ *
+ * cap_dgram256     G = Q^T Q for Q m x 256: the upper triangle of the 256 x 256 square of G is written, its strictly-lower part is
+ *                  set to 0.0, rows >= 256 of G (ldg > 256) and Q are not touched.  min(CUs, m / 512, max_wgs) (at least one) workgroups
+ *                  own one slab of rows each, their partial Grams go through `work` (one 256 x 256 slab per workgroup, every slab
+ *                  written, also by a workgroup without rows) and are added in a fixed order: two calls give the same bits.
+ *                  m > 0, m % 16 == 0, ldq >= m and even, Q 16-byte aligned, ldg >= 256 (odd allowed), 128 * ldq * 8 < 0xfffffff0
+ *                  (ldq <= 4194302: the kernel's 32-bit byte offsets), non-NULL Q, G, work; work >= cap_dgram256_work_size(m)
+ *                  doubles (the uncapped slab count; 0 for m <= 0).  G and work must not overlap Q or each other.
+ * cap_dqrapply256  Qout = Qin * Ri for Qin, Qout m x 256 and Ri 256 x 256 with leading dimension 256, upper triangular with its
+ *                  strictly-lower part ZERO inside the 16 x 16 diagonal blocks (read as stored); the 16 x 16 blocks below the block
+ *                  diagonal are never read.  min(CUs, m / 128, max_wgs) persistent workgroups walk consecutive row tiles of 128
+ *                  rows.  Rows >= m of Qout (ldout > m) are not touched.  In place (Qout == Qin, ldout == ldin) is allowed; any other
+ *                  overlap is not.  m > 0, m % 128 == 0, ldin >= m and even, ldout >= m, Qin and Ri 16-byte aligned (Qout: 8),
+ *                  ldin and ldout <= 35791385 (15 * ld * 8 + 1024 < 0xfffffff0: rows of a tile are addressed by 32-bit byte
+ *                  offsets of up to 15 columns), non-NULL Qin, Ri, Qout.                                                            */
+int64_t cap_dgram256_work_size(int64_t m);
+int cap_dgram256(int64_t m, const double* Q, int64_t ldq, double* G, int64_t ldg, double* work, int64_t max_wgs, void* stream);
+int cap_dqrapply256(int64_t m, const double* Qin, int64_t ldin, const double* Ri, double* Qout, int64_t ldout, int64_t max_wgs,
+                    void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Matrix descriptor helpers (replaces src/matrix/: generators, serialize, structure)
  * ---------------------------------------------------------------------------------- */
