@@ -398,6 +398,32 @@ void k_leaf_trtri(void** a) {
   trtri_upper(S.data(), n, T.data(), n, n);
   for (int j = 0; j < n; j++) for (int i = 0; i <= j; i++) Ri[i + j * ldi] = T[i + (size_t)j * n];
 }
+// lauum.hip, dlauum_nt_kernel: C[i][j] = sum_{k >= j} W[i][k] W[j][k] for i <= j on the T x T tiles of 128; block b runs on XCD b % 8, which
+// walks the tile columns tj = b % 8, b % 8 + 8, ... rows ascending (LauumArgs is local to lauum.hip: the same layout here); nothing below
+// the diagonal of W is read, nothing below that of C written
+struct LauumArgsModel { const double* W; double* C; int64_t ldw, ldc; int T; };
+void k_dlauum_nt(void** a, unsigned gx) {
+  const LauumArgsModel g = arg<LauumArgsModel>(a, 0);
+  const int64_t n = (int64_t)g.T * 128;
+  std::vector<std::pair<int, int>> tiles;
+  for (unsigned b = 0; b < gx; b++) {
+    int s = (int)(b >> 3);
+    for (int c = (int)(b & 7); c < g.T; c += 8) {
+      if (s <= c) { tiles.push_back({s, c}); break; }
+      s -= c + 1;
+    }
+  }
+#pragma omp parallel for schedule(dynamic)
+  for (size_t t = 0; t < tiles.size(); t++) {          // (every tile of a launch has one writer)
+    const int64_t i0 = (int64_t)tiles[t].first * 128, j0 = (int64_t)tiles[t].second * 128;
+    for (int64_t j = j0; j < j0 + 128; j++)
+      for (int64_t i = i0; i < i0 + 128 && i <= j; i++) {
+        double s = 0.0;
+        for (int64_t k = j; k < n; k++) s += g.W[i + k * g.ldw] * g.W[j + k * g.ldw];
+        g.C[i + j * g.ldc] = s;
+      }
+  }
+}
 // X (64 x 64) = Dinv^T B with Dinv upper (only its upper triangle is read)
 void solve64(const double* Dinv, int64_t ldi, const double* B, int64_t ldb, double* X) {
   for (int c = 0; c < 64; c++)
@@ -800,6 +826,7 @@ static int dispatch(const char* mangled, void** args, unsigned gx, unsigned gy, 
   if (has("cyclic_piece_kernel")) { k_cyclic_piece(args); return 1; }
   if (has("leaf_cholinv_kernel")) { k_leaf_cholinv(args); return 1; }
   if (has("leaf_trtri_kernel")) { k_leaf_trtri(args); return 1; }
+  if (has("dlauum_nt_kernel")) { k_dlauum_nt(args, gx); return 1; }
   if (has("panel64_solve_update_kernel")) { k_panel64(args, gx); return 1; }
   if (has("trinv_merge_kernel")) { k_trinv_merge(n, args, gy); return 1; }
   if (has("chain64_coop_kernel")) { k_chain64(args); return 1; }
