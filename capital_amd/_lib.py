@@ -31,6 +31,8 @@ SIGNATURES = {
     "cap_dpotrf_work_size": (i64, [i64]),
     "cap_dpotrs": (cint, [cint, i64, i64, ptr, i64, ptr, i64, ptr, ptr]),
     "cap_dpotrs_work_size": (i64, [i64, i64]),
+    "cap_dpotrf_batched": (cint, [cint, i64, ptr, i64, i64, i64, ptr, ptr, ptr]),
+    "cap_dpotrs_batched": (cint, [cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

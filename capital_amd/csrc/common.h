@@ -202,6 +202,12 @@ int cap_chud_run(int sign, int64_t n, int64_t k, double* R, int64_t ldr, const d
 int64_t cap_pstrf_work_size(int64_t n, int64_t max_rank);
 int cap_pstrf_run(int64_t n, int64_t max_rank, double tol, const double* A, int64_t lda, double* R, int64_t ldr, int64_t* piv,
                   int64_t* rank, double* resid, int* info, double* work, hipStream_t s);
+// potrf_batched.hip: batch blocks of n <= 64 at A + i stride_a factored in place (upper), one launch, one wavefront per 64 / NP blocks;
+// info / logdet: batch entries each, may be NULL.  The solve with those factors: B_i (n x nrhs at B + i stride_b) <- A_i^-1 B_i, NaN where
+// info != NULL and info[i] != 0.  Neither takes scratch or touches process-wide state.
+int cap_potrf_batched_launch(int64_t n, double* A, int64_t lda, int64_t stride_a, int64_t batch, int* info, double* logdet, hipStream_t s);
+int cap_potrs_batched_launch(int64_t n, int64_t nrhs, const double* R, int64_t ldr, int64_t stride_r, double* B, int64_t ldb, int64_t stride_b,
+                             int64_t batch, const int* info, hipStream_t s);
 // pocon.hip: LAPACK's dlacn2 for diag(w) A^-1 and its transpose, nc <= 16 columns in lock-step (w = W[:, c], W == NULL: ones), A = R^T R with
 // Inv the inverses of R's diagonal blocks of cap_potrs_block() rows.  In front: the start vectors and, when Res != NULL, the dporfs quantities
 // of the columns - berr (may be NULL) from Res = B - A X and Den = |A||X| + |B| (n x nc, leading dimension ldv = cap_pocon_ld(n); Den is

@@ -2,7 +2,8 @@
 
 _potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor), _cholupdate (that factor after A +- V V^T), _pstrf (the
 pivoted factorization of a semidefinite A, LAPACK's dpstrf), _lansy (the 1-norm of a symmetric matrix), _pocon (the reciprocal condition
-number from the factor, LAPACK's dpocon) and _poerr (the error bounds of LAPACK's dporfs) have no counterpart upstream.
+number from the factor, LAPACK's dpocon), _poerr (the error bounds of LAPACK's dporfs) and _potrf_batched / _potrs_batched (the factor and
+solve of many small blocks of one size in one launch) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -40,6 +41,8 @@ class Method(enum.IntEnum):
     AlapackLansy = 0x6          # extension: not in the reference's enum
     AlapackPocon = 0x7          # extension: not in the reference's enum
     AlapackPoerr = 0x8          # extension: not in the reference's enum
+    AlapackPotrfBatched = 0x9   # extension: not in the reference's enum
+    AlapackPotrsBatched = 0xA   # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
 
@@ -89,6 +92,18 @@ class ArgPack_pocon:
 class ArgPack_poerr:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPoerr
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_potrf_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotrfBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_potrs_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotrsBatched
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -205,6 +220,38 @@ class engine:
                           ferr.data_ptr(), berr.data_ptr(), dptr(work), cur_stream(stream))
         _lib.check(st, "lapack::engine::_poerr")
         return ferr[:nrhs], berr[:nrhs]
+
+    @staticmethod
+    def _potrf_batched(matrixA, n, lda, stride, batch, srcPackage, want_logdet=False, stream=None):
+        """The n x n blocks (n <= 64, column-major, ld lda) at matrixA + i stride, i < batch, <- their upper factors, in one launch.  Returns
+        (info, logdet): an int32 device tensor of batch entries (0, or the 1-based first pivot that is not > 0; such a block holds NaN from
+        that row on) and, with want_logdet, an fp64 one with 2 sum log r_jj (NaN for a failed block), else None.  Nothing is read back:
+        asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        a = dptr(matrixA)
+        dev = matrixA.device if isinstance(matrixA, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        info = torch.zeros(max(batch, 1), dtype=torch.int32, device=dev)
+        logdet = torch.zeros(max(batch, 1), dtype=torch.float64, device=dev) if want_logdet else None
+        st = L.cap_dpotrf_batched(int(srcPackage.uplo), n, a, lda, stride, batch, info.data_ptr(),
+                                  logdet.data_ptr() if want_logdet else None, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrf_batched")
+        return info[:max(batch, 0)], (logdet[:max(batch, 0)] if want_logdet else None)
+
+    @staticmethod
+    def _potrs_batched(matrixR, matrixB, n, nrhs, ldr, stride_r, ldb, stride_b, batch, info, srcPackage, stream=None):
+        """B_i (n x nrhs, ld ldb, at matrixB + i stride_b) <- A_i^-1 B_i with A_i = R_i^T R_i, R_i the upper factor _potrf_batched left at
+        matrixR + i stride_r (ld ldr).  info: what _potrf_batched returned, or None; a block with info != 0 gets NaN.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        if info is not None and (not isinstance(info, torch.Tensor) or not info.is_cuda or info.dtype != torch.int32
+                                 or info.numel() < batch or not info.is_contiguous()):
+            raise _lib.CapitalError("info must be a contiguous int32 device tensor of batch entries")
+        L = _lib.lib()
+        st = L.cap_dpotrs_batched(int(srcPackage.uplo), n, nrhs, dptr(matrixR), ldr, stride_r, dptr(matrixB), ldb, stride_b, batch,
+                                  info.data_ptr() if info is not None else None, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrs_batched")
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

@@ -165,6 +165,30 @@ int cap_dpstrf(int uplo, int64_t n, int64_t max_rank, double tol, const double* 
                int64_t* rank, double* resid, int* info, double* work, void* stream);
 int64_t cap_dpstrf_work_size(int64_t n, int64_t max_rank);
 
+/* Batched Cholesky factor and solve for MANY SMALL SPD matrices of one size (potrf_batched / potrs_batched of the vendor libraries, strided
+ * form; not in the reference): matrix i is the n x n column-major block at A + i * stride_a (leading dimension lda), i = 0 .. batch - 1,
+ * 1 <= n <= 64 - n > 64 returns CAP_ERR_UNSUPPORTED (loop over cap_dpotrf for larger blocks).  fp64, upper factor, one GPU, ONE launch per
+ * call (csrc/potrf_batched.hip: one wavefront per 64 / NP blocks, NP = 8, 16, 32 or 64 >= n; nothing between workgroups).  No `work`
+ * argument, no allocation, no process-wide state (no mutex, no helper stream): asynchronous on `stream`, callable from several host threads.
+ * cap_dpotrf_batched: the upper triangle of every block is replaced by R_i (A_i = R_i^T R_i).  The strictly lower triangles, rows n .. lda - 1
+ * of every column, the gaps between blocks (stride_a > lda n) and everything behind the last block are neither read nor written.
+ * info (batch device ints, may be NULL): info[i] = 0, or the 1-based index p of the first pivot that is not > 0 (a NaN pivot counts as not
+ * > 0).  Such a block holds the rows 0 .. p - 2 of R computed so far and NaN in rows p - 1 .. n - 1 of its upper triangle; no other block is
+ * affected.  logdet (batch device doubles, may be NULL): logdet[i] = 2 sum_j log r_jj, added in ascending j; NaN for a failed block.
+ * Square roots and divisions are correctly rounded ones, no reciprocal estimates.
+ * cap_dpotrs_batched: B_i (n x nrhs at B + i * stride_b, leading dimension ldb) <- the solution of R_i^T R_i X = B_i, any nrhs >= 0 (more
+ * than NP right-hand sides are further passes inside the launch).  The strictly lower triangle of R is not referenced; only rows 0 .. n - 1
+ * of the nrhs columns of each B_i are written.  info (what the factor call wrote, may be NULL): info[i] != 0 leaves X_i NaN, the convention
+ * of cap_cholinv_solve.
+ * A block's result bits depend on (n, its own data) alone - not on batch, its index, lda, the strides, the alignment, the number of
+ * right-hand sides that travel with a column, or the run.
+ * n < 0, batch < 0, nrhs < 0; a NULL A / R / B with n batch > 0; lda, ldr or ldb < n; with batch > 1: stride_a < lda n, stride_r < ldr n or
+ * stride_b < ldb nrhs -> CAP_ERR_ARG; then uplo = LOWER -> CAP_ERR_UNSUPPORTED, as cap_dpotrf; then n > 64 -> CAP_ERR_UNSUPPORTED; n == 0,
+ * batch == 0 or nrhs == 0 -> CAP_OK without a launch.  All decided before any device call.  Offsets are 64-bit.                            */
+int cap_dpotrf_batched(int uplo, int64_t n, double* A, int64_t lda, int64_t stride_a, int64_t batch, int* info, double* logdet, void* stream);
+int cap_dpotrs_batched(int uplo, int64_t n, int64_t nrhs, const double* R, int64_t ldr, int64_t stride_r, double* B, int64_t ldb,
+                       int64_t stride_b, int64_t batch, const int* info, void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
