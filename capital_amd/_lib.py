@@ -33,6 +33,8 @@ SIGNATURES = {
     "cap_dpotrs_work_size": (i64, [i64, i64]),
     "cap_dpotrf_batched": (cint, [cint, i64, ptr, i64, i64, i64, ptr, ptr, ptr]),
     "cap_dpotrs_batched": (cint, [cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
+    "cap_dpotrf_batched_blocked": (cint, [cint, i64, ptr, i64, i64, i64, ptr, ptr, ptr]),
+    "cap_dpotrs_batched_blocked": (cint, [cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

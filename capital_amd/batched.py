@@ -1,6 +1,8 @@
 """Many small SPD systems of one size on plain torch tensors: one launch factors (potrf) or solves (potrs) the whole batch.
 
-The tensors are the memory the C ABI works on (cap_dpotrf_batched / cap_dpotrs_batched, csrc/potrf_batched.hip): fp64, on the device, n <= 64.
+The tensors are the memory the C ABI works on: fp64, on the device, n <= 256 (n <= 64: cap_dpotrf_batched / cap_dpotrs_batched,
+csrc/potrf_batched.hip, a wavefront per block; 64 < n <= 256: cap_dpotrf_batched_blocked / cap_dpotrs_batched_blocked,
+csrc/potrf_batched_blocked.hip, a workgroup per block).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import torch
 
@@ -34,7 +36,7 @@ def _blocks(A, name):
 
 
 def potrf(A, logdet=False):
-    """Cholesky factors of the batch, in place.  A: fp64 device tensor of shape (batch, n, n), n <= 64, with stride(2) == 1; stride(1) >= n and
+    """Cholesky factors of the batch, in place.  A: fp64 device tensor of shape (batch, n, n), n <= 256, with stride(2) == 1; stride(1) >= n and
     stride(0) >= n stride(1) are free.  Each A[i] is read as COLUMN-MAJOR memory with leading dimension stride(1) and its upper factor R
     (A = R^T R) replaces the upper triangle of that column-major block.  In torch's row-major reading of the same memory this means: the
     LOWER triangle of A[i] then holds L = torch.linalg.cholesky(A)[i] (L = R^T) and the upper triangle of A[i] is untouched - the input must

@@ -107,6 +107,17 @@ class ArgPack_potrs_batched:
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
+BATCHED_SMALL_MAX = 64      # cap_dpotrf_batched / cap_dpotrs_batched: a wavefront per block
+BATCHED_MAX = 256           # cap_dpotrf_batched_blocked / cap_dpotrs_batched_blocked: a workgroup per block
+
+
+def _batched_blocked(L, n):
+    """the library, once n is known to be within the batched calls' limit"""
+    if n > BATCHED_MAX:
+        raise _lib.CapitalError("batched Cholesky: blocks of n = %d rows exceed the limit of %d rows per block" % (n, BATCHED_MAX))
+    return L
+
+
 class ArgPack_trtri:
     def __init__(self, order, uplo, diag):
         self.method = Method.AlapackTrtri
@@ -223,34 +234,36 @@ class engine:
 
     @staticmethod
     def _potrf_batched(matrixA, n, lda, stride, batch, srcPackage, want_logdet=False, stream=None):
-        """The n x n blocks (n <= 64, column-major, ld lda) at matrixA + i stride, i < batch, <- their upper factors, in one launch.  Returns
+        """The n x n blocks (n <= 256, column-major, ld lda) at matrixA + i stride, i < batch, <- their upper factors, in one launch (n <= 64:
+        cap_dpotrf_batched, a wavefront per block; 64 < n <= 256: cap_dpotrf_batched_blocked, a workgroup per block).  Returns
         (info, logdet): an int32 device tensor of batch entries (0, or the 1-based first pivot that is not > 0; such a block holds NaN from
         that row on) and, with want_logdet, an fp64 one with 2 sum log r_jj (NaN for a failed block), else None.  Nothing is read back:
         asynchronous."""
         if srcPackage.order != Order.AlapackColumnMajor:
             raise _lib.CapitalError("only AlapackColumnMajor is supported")
         L = _lib.lib()
+        fn = L.cap_dpotrf_batched if n <= BATCHED_SMALL_MAX else _batched_blocked(L, n).cap_dpotrf_batched_blocked
         a = dptr(matrixA)
         dev = matrixA.device if isinstance(matrixA, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
         info = torch.zeros(max(batch, 1), dtype=torch.int32, device=dev)
         logdet = torch.zeros(max(batch, 1), dtype=torch.float64, device=dev) if want_logdet else None
-        st = L.cap_dpotrf_batched(int(srcPackage.uplo), n, a, lda, stride, batch, info.data_ptr(),
-                                  logdet.data_ptr() if want_logdet else None, cur_stream(stream))
+        st = fn(int(srcPackage.uplo), n, a, lda, stride, batch, info.data_ptr(), logdet.data_ptr() if want_logdet else None, cur_stream(stream))
         _lib.check(st, "lapack::engine::_potrf_batched")
         return info[:max(batch, 0)], (logdet[:max(batch, 0)] if want_logdet else None)
 
     @staticmethod
     def _potrs_batched(matrixR, matrixB, n, nrhs, ldr, stride_r, ldb, stride_b, batch, info, srcPackage, stream=None):
         """B_i (n x nrhs, ld ldb, at matrixB + i stride_b) <- A_i^-1 B_i with A_i = R_i^T R_i, R_i the upper factor _potrf_batched left at
-        matrixR + i stride_r (ld ldr).  info: what _potrf_batched returned, or None; a block with info != 0 gets NaN.  Asynchronous."""
+        matrixR + i stride_r (ld ldr), n <= 256.  info: what _potrf_batched returned, or None; a block with info != 0 gets NaN.  Asynchronous."""
         if srcPackage.order != Order.AlapackColumnMajor:
             raise _lib.CapitalError("only AlapackColumnMajor is supported")
         if info is not None and (not isinstance(info, torch.Tensor) or not info.is_cuda or info.dtype != torch.int32
                                  or info.numel() < batch or not info.is_contiguous()):
             raise _lib.CapitalError("info must be a contiguous int32 device tensor of batch entries")
         L = _lib.lib()
-        st = L.cap_dpotrs_batched(int(srcPackage.uplo), n, nrhs, dptr(matrixR), ldr, stride_r, dptr(matrixB), ldb, stride_b, batch,
-                                  info.data_ptr() if info is not None else None, cur_stream(stream))
+        fn = L.cap_dpotrs_batched if n <= BATCHED_SMALL_MAX else _batched_blocked(L, n).cap_dpotrs_batched_blocked
+        st = fn(int(srcPackage.uplo), n, nrhs, dptr(matrixR), ldr, stride_r, dptr(matrixB), ldb, stride_b, batch,
+                info.data_ptr() if info is not None else None, cur_stream(stream))
         _lib.check(st, "lapack::engine::_potrs_batched")
 
     @staticmethod

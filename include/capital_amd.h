@@ -189,6 +189,19 @@ int cap_dpotrf_batched(int uplo, int64_t n, double* A, int64_t lda, int64_t stri
 int cap_dpotrs_batched(int uplo, int64_t n, int64_t nrhs, const double* R, int64_t ldr, int64_t stride_r, double* B, int64_t ldb,
                        int64_t stride_b, int64_t batch, const int* info, void* stream);
 
+/* The same two calls for blocks of up to 256 rows: 1 <= n <= 256, n > 256 returns CAP_ERR_UNSUPPORTED.  Arguments, layout, info / logdet,
+ * the argument rules and their order are those of cap_dpotrf_batched / cap_dpotrs_batched (which keep refusing n > 64).  n <= 64 runs the
+ * kernels of those calls: the same bits.  64 < n <= 256 (csrc/potrf_batched_blocked.hip): ONE launch, one workgroup of four waves per block on
+ * a 1-D grid (batch beyond one grid dimension -> CAP_ERR_UNSUPPORTED), nothing between workgroups; a right-looking factorization over diagonal
+ * blocks of 64 rows - the diagonal block in one wave's registers, the row panel by substitution with a column per lane, the trailing update
+ * on the fp64 MFMA from LDS - and blocked substitutions with 16 right-hand sides per pass.  No `work`, no allocation, no memset, no mutex, no
+ * helper stream, no host synchronisation.  What is never read or written, the NaN rows of a failed block, correctly rounded square roots and
+ * divisions, and "a block's bits depend on (n, its own data) alone, a column's on (n, R, that column of B) alone": as above.               */
+int cap_dpotrf_batched_blocked(int uplo, int64_t n, double* A, int64_t lda, int64_t stride_a, int64_t batch, int* info, double* logdet,
+                               void* stream);
+int cap_dpotrs_batched_blocked(int uplo, int64_t n, int64_t nrhs, const double* R, int64_t ldr, int64_t stride_r, double* B, int64_t ldb,
+                               int64_t stride_b, int64_t batch, const int* info, void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
