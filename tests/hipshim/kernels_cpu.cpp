@@ -85,9 +85,9 @@ constexpr int TB = 128, TK = 16;
 std::mutex modes_mu;
 std::vector<std::string> gemm_modes;
 void log_modes(const GemmArgs& g) {
-  char buf[256];
-  snprintf(buf, sizeof(buf), "ksplit=%d skip=%d stm=%d stn=%d sorder=%d etri=%d tri=%d bupper=%d aupt=%d aupn=%d usebuf=%d tm=%d tn=%d",
-           g.ksplit, g.skip, g.stm, g.stn, g.sorder, g.etri, g.tri, g.bupper, g.aupt, g.aupn, g.usebuf, g.tm, g.tn);
+  char buf[320];
+  snprintf(buf, sizeof(buf), "ksplit=%d skip=%d stm=%d stn=%d sorder=%d etri=%d tri=%d bupper=%d aupt=%d aupn=%d usebuf=%d tm=%d tn=%d cin=%d k=%lld",
+           g.ksplit, g.skip, g.stm, g.stn, g.sorder, g.etri, g.tri, g.bupper, g.aupt, g.aupn, g.usebuf, g.tm, g.tn, (int)(g.Cin != g.C), (long long)g.K);
   std::lock_guard<std::mutex> lk(modes_mu);
   gemm_modes.emplace_back(buf);
 }
