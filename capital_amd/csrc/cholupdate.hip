@@ -329,16 +329,19 @@ int launch_pass(ChudArgs g, bool one, hipStream_t s) {
     hipLaunchKernelGGL(chud_sweep_kernel<NK>, dim3((unsigned)std::max(1, std::min(items, resident_wgs()))), dim3(UT), 0, s, g);
     CAP_HIP(hipGetLastError());
     g.mode = 1;
+    cap_acc_none();                   // (the pass was noted once, in front of its first launch: cap_chud_run)
     hipLaunchKernelGGL(chud_sweep_kernel<NK>, dim3(1), dim3(UT), 0, s, g);
     CAP_HIP(hipGetLastError());
     return CAP_OK;
   }
   for (int j = 0; j < nb; j++) {
     g.j0 = j; g.mode = 2;
+    if (j > 0) cap_acc_none();        // (the pass was noted once, in front of its first launch: cap_chud_run)
     hipLaunchKernelGGL(chud_step_kernel<NK>, dim3(1), dim3(UT), 0, s, g);
     CAP_HIP(hipGetLastError());
     if (j + 1 < nb) {
       g.mode = 3;
+      cap_acc_none();
       hipLaunchKernelGGL(chud_step_kernel<NK>, dim3((unsigned)(nb - 1 - j)), dim3(UT), 0, s, g);
       CAP_HIP(hipGetLastError());
     }

@@ -297,7 +297,7 @@ int cap_pocon_run(int64_t n, int64_t nc, const double* R, int64_t ldr, const dou
   hipLaunchKernelGGL(pocon_init_kernel, dim3((unsigned)nc), dim3(PC_T), 0, s, g);
   CAP_HIP(hipGetLastError());
   if (!want_est) return CAP_OK;
-  if (cap_acc_on()) cap_acc_w(ctr, 0, PC_SOLVES * 2 * cw, 1, 0, 4);
+  // (no access note: a memset is no launch, the replay's stand-in records the window of a memset itself)
   CAP_HIP(hipMemsetAsync(ctr, 0, sizeof(int) * PC_SOLVES * 2 * cw, s));         // the counters of all 22 substitutions, once
   const int* skip = &g.ctl->skip;
   for (int k = 0; k < PC_SOLVES; k++) {

@@ -9,7 +9,14 @@
  *  - all matrices are COLUMN-MAJOR fp64 in DEVICE memory (HBM), caller owned;
  *  - dimensions / leading dimensions are int64_t (blas/interface.h:58-66 uses int64_t);
  *  - `stream` is a hipStream_t passed as void* (NULL = the null stream); every call is
- *    asynchronous on that stream unless stated otherwise;
+ *    asynchronous on that stream unless stated otherwise.  "No host synchronisation" below is
+ *    about the steady state, with two exceptions that hold for every entry: (1) the FIRST call
+ *    of a process on a device that needs one of the small per-device word blocks (the give-up /
+ *    injection counters of cap_dpotrs, cap_cholinv_solve, cap_dpocon, cap_dpoerr, cap_dcholupdate,
+ *    cap_cholinv_update and of the diagonal-block chain) allocates and zeroes it and synchronises
+ *    the device once; (2) scratch that a PLAN keeps is allocated by the first call that needs it
+ *    and sized for that call - a later call on the same plan that needs MORE synchronises the
+ *    device once, frees it and allocates the larger one (see cap_cholinv_solve);
  *  - every function returns a cap_status (0 = ok).  The reference has no error channel
  *    (LAPACKE info is dropped, lapack/interface.hpp:39,54); here POTRF's `info` is
  *    propagated through a device-resident int the caller can read back.
@@ -533,7 +540,13 @@ double* cap_cholinv_Rinv_ptr(cap_cholinv_plan* plan, int64_t* ld);
  * (forward R^T Y = B into plan scratch, backward R X = Y), workgroups claiming the blocks' diagonal steps and tile products from a
  * ticket counter, each launch followed by a recovery launch that redoes the substitution on one workgroup if a workgroup of it
  * gave up waiting (counted by cap_solve_fallbacks); option "solve_kernel" = 0 sends these to the blocked path that more
- * right-hand sides take (cap_dtrsm's substitution: MFMA GEMMs per block step).                                              */
+ * right-hand sides take (cap_dtrsm's substitution: MFMA GEMMs per block step).
+ * PLAN SCRATCH AND THE ONE HOST SYNCHRONISATION IT CAN COST.  cap_cholinv_solve, _update, _rcond and _error_bounds keep their scratch and
+ * the block inverses in the plan, allocated by the first call that needs them and sized for that call (no synchronisation).  A later call
+ * that needs more - more right-hand sides, the other substitution path and its block width (nrhs > 16 or "solve_kernel" = 0 after the
+ * one-launch path), cap_cholinv_error_bounds after cap_cholinv_rcond, a larger k - waits for the device (hipDeviceSynchronize: the old
+ * buffer may still be in use), frees the buffer and allocates the larger one.  Buffers never shrink, so a given sequence of calls
+ * synchronises at most on its first pass over a plan; a caller that cannot afford even that makes its largest call first.           */
 int cap_cholinv_solve(cap_cholinv_plan* plan, const double* B, int64_t ldb, double* X, int64_t ldx,
                       int64_t nrhs, void* stream);
 /* A^-1 of the plan's LAST factor call into out (n x n, column-major, device).  fill = 0: upper triangle only, the rest of out untouched;

@@ -140,8 +140,10 @@ class Run:
         if user_stream:
             ok(shim.hipStreamCreateWithFlags(C.byref(self.stream), 1), "hipStreamCreateWithFlags")
         self.uid = 1 if user_stream else 0          # (the stand-in numbers streams from 1 after every process start - see finish())
+        self.entries = set()                        # the C ABI entries this scenario called under a mark
 
     def call(self, what, fn, *args):
+        self.entries.add(getattr(fn, "__name__", ""))
         shim.shim_mark(("begin %s" % what).encode())
         st = fn(*args)
         shim.shim_mark(("end %s user=@" % what).encode())
@@ -178,7 +180,7 @@ class Run:
         if self.stream.value:
             shim.hipStreamDestroy(self.stream)
         stats["oob"] = int(shim.shim_oob())
-        return {"name": self.name, "findings": findings, "stats": stats}
+        return {"name": self.name, "findings": findings, "stats": stats, "entries": sorted(self.entries - {""})}
 
 
 RESULTS = []
@@ -332,6 +334,142 @@ def cacqr_case(r, m, n, iters, P, p):
     r.call("cacqr_info", L.cap_cacqr_info, plan, r.stream, C.byref(info))
     ok(L.cap_cacqr_plan_destroy(plan), "cap_cacqr_plan_destroy")
     comm.close(); shim.hipFree(A)
+
+
+def cacqr_solve_case(r, m, n, iters):
+    """factor -> shift -> solve -> apply_qt -> factor -> solve on one 1D plan: the slab buffer and the solve's scratch are allocated by
+    the first call that needs them, the block inverses of R by the first solve after each factor"""
+    plan = C.c_void_p()
+    ok(L.cap_cacqr_plan_create(C.byref(plan), m, n, iters, None), "cap_cacqr_plan_create")
+    A = dmalloc(8 * m * n); B = dmalloc(8 * m * 100); X = dmalloc(8 * n * 100); Z = dmalloc(8 * n * 100)
+    sh = C.c_double(0)
+    ok(r.call("cacqr_factor", L.cap_cacqr_factor, plan, A, m, r.stream), "cap_cacqr_factor")
+    ok(r.call("cacqr_solve nrhs=3", L.cap_cacqr_solve, plan, B, m, 3, X, n, r.stream), "cap_cacqr_solve")
+    ok(r.call("cacqr_apply_qt nrhs=17", L.cap_cacqr_apply_qt, plan, B, m, 17, Z, n, r.stream), "cap_cacqr_apply_qt")
+    ok(r.call("cacqr_shift", L.cap_cacqr_shift, plan, C.byref(sh), r.stream), "cap_cacqr_shift")
+    ok(r.call("cacqr_factor", L.cap_cacqr_factor, plan, A, m, r.stream), "cap_cacqr_factor")
+    ok(r.call("cacqr_solve nrhs=100", L.cap_cacqr_solve, plan, B, m, 100, X, n, r.stream), "cap_cacqr_solve")
+    ok(r.call("cacqr_apply_qt nrhs=8", L.cap_cacqr_apply_qt, plan, B, m, 8, Z, n, r.stream), "cap_cacqr_apply_qt")
+    ok(L.cap_cacqr_plan_destroy(plan), "cap_cacqr_plan_destroy")
+    for q in (A, B, X, Z):
+        shim.hipFree(q)
+
+
+def cholinv_sequence_case(r, n, ci, opts=()):
+    """one plan, every call behind the other WITHOUT a host synchronisation in between: the solves, the inverse, rcond and the error bounds
+    share the plan's block inverses ("whichever runs first makes them"), its scratch (allocated on first use) and its helper streams with
+    the factor; the update (complete_inv = -1 only) rewrites the resident R under them"""
+    plan = C.c_void_p()
+    ok(L.cap_cholinv_plan_create(C.byref(plan), n, ci, 1, 0, b"U", None), "cap_cholinv_plan_create")
+    for k, v in opts:
+        ok(L.cap_cholinv_set_option(plan, k.encode(), v), "set_option " + k)
+    A = dmalloc(8 * n * n); out = dmalloc(8 * n * n); B = dmalloc(8 * n * 17); X = dmalloc(8 * n * 17); V = dmalloc(8 * n * 17)
+    small = dmalloc(8 * 64)
+    ld_, rc_, fe_, be_ = small.value, small.value + 8, small.value + 16, small.value + 16 + 8 * 17
+
+    def solve(nrhs, inplace=False):
+        ok(r.call("cholinv_solve nrhs=%d" % nrhs, L.cap_cholinv_solve, plan, B, n, B if inplace else X, n, nrhs, r.stream), "cap_cholinv_solve")
+
+    def tail():
+        ok(r.call("cholinv_rcond", L.cap_cholinv_rcond, plan, A, n, None, rc_, r.stream), "cap_cholinv_rcond")
+        ok(r.call("cholinv_rcond (norm given)", L.cap_cholinv_rcond, plan, None, 0, ld_, rc_, r.stream), "cap_cholinv_rcond")
+        ok(r.call("cholinv_error_bounds nrhs=3", L.cap_cholinv_error_bounds, plan, A, n, B, n, X, n, 3, fe_, be_, r.stream), "cap_cholinv_error_bounds")
+        ok(r.call("cholinv_error_bounds nrhs=17", L.cap_cholinv_error_bounds, plan, A, n, B, n, X, n, 17, fe_, be_, r.stream), "cap_cholinv_error_bounds")
+        ok(r.call("cholinv_factor", L.cap_cholinv_factor, plan, A, n, r.stream), "cap_cholinv_factor")
+        solve(3)
+    ok(r.call("cholinv_factor", L.cap_cholinv_factor, plan, A, n, r.stream), "cap_cholinv_factor")
+    solve(3); solve(17)
+    ok(r.call("cholinv_logdet", L.cap_cholinv_logdet, plan, ld_, r.stream), "cap_cholinv_logdet")
+    ok(r.call("cholinv_inverse fill=1", L.cap_cholinv_inverse, plan, out, n, 1, r.stream), "cap_cholinv_inverse")
+    if ci == -1:
+        ok(r.call("cholinv_update +V k=3", L.cap_cholinv_update, plan, 1, V, n, 3, r.stream), "cap_cholinv_update")
+        solve(3)
+        ok(r.call("cholinv_update -V k=3", L.cap_cholinv_update, plan, -1, V, n, 3, r.stream), "cap_cholinv_update")
+        solve(3, inplace=True)
+        for k in (17, 1, 16):            # two passes, the one-column instance, one full pass (with option "chud_kernel" = 0: the stepwise driver)
+            ok(r.call("cholinv_update +V k=%d" % k, L.cap_cholinv_update, plan, 1, V, n, k, r.stream), "cap_cholinv_update")
+        ok(r.call("cholinv_inverse fill=0", L.cap_cholinv_inverse, plan, out, n, 0, r.stream), "cap_cholinv_inverse")
+    tail()
+    info = C.c_int64(0)
+    r.call("cholinv_info", L.cap_cholinv_info, plan, r.stream, C.byref(info))
+    ok(L.cap_cholinv_plan_destroy(plan), "cap_cholinv_plan_destroy")
+    for q in (A, out, B, X, V, small):
+        shim.hipFree(q)
+
+
+def lapack_extras_case(r, n):
+    """the plan-less entries beside cap_dpotrf on the caller's stream, each at the sizes that reach its launch routes: POTRS (one launch up
+    to 16 right-hand sides, blocked beyond), POTRI / LAUUM, the rank-k update (1, 16 and 17 columns: one and two passes), pivoted
+    Cholesky with a rank cap, POCON, the error bounds (1 and 17 columns), the 1-norm and the thin symmetric product"""
+    U = 1
+    A = dmalloc(8 * n * n); R = dmalloc(8 * n * n); Cc = dmalloc(8 * n * n); B = dmalloc(8 * n * 17); X = dmalloc(8 * n * 17); Y = dmalloc(8 * n * 17)
+    small = dmalloc(8 * 64); piv = dmalloc(8 * n)
+    an_, rc_, fe_, be_, rk_, rs_, inf_ = (small.value + 8 * i for i in (0, 1, 2, 20, 40, 41, 42))
+    for nrhs in (1, 16, 17):
+        W = dmalloc(8 * max(int(L.cap_dpotrs_work_size(n, nrhs)), 1))
+        ok(r.call("dpotrs nrhs=%d" % nrhs, L.cap_dpotrs, U, n, nrhs, R, n, B, n, W, r.stream), "cap_dpotrs")
+        shim.hipFree(W)
+    ok(r.call("dlauum", L.cap_dlauum, U, n, R, n, Cc, n, r.stream), "cap_dlauum")
+    W = dmalloc(8 * max(int(L.cap_dpotri_work_size(n)), 1))
+    ok(r.call("dpotri", L.cap_dpotri, U, n, Cc, n, W, r.stream), "cap_dpotri")
+    shim.hipFree(W)
+    for k in (1, 16, 17):
+        for sign in (1, -1):
+            W = dmalloc(8 * max(int(L.cap_dcholupdate_work_size(n, k)), 1))
+            ok(r.call("dcholupdate sign=%d k=%d" % (sign, k), L.cap_dcholupdate, U, sign, n, k, R, n, X, n, inf_, W, r.stream), "cap_dcholupdate")
+            shim.hipFree(W)
+    cap = min(n, 24)
+    W = dmalloc(8 * max(int(L.cap_dpstrf_work_size(n, cap)), 1))
+    ok(r.call("dpstrf max_rank=%d" % cap, L.cap_dpstrf, U, n, cap, -1.0, A, n, Cc, n, piv, rk_, rs_, inf_, W, r.stream), "cap_dpstrf")
+    shim.hipFree(W)
+    W = dmalloc(8 * max(int(L.cap_dlansy_work_size(n)), 1))
+    ok(r.call("dlansy", L.cap_dlansy, ord("1"), U, n, A, n, an_, W, r.stream), "cap_dlansy")
+    shim.hipFree(W)
+    W = dmalloc(8 * max(int(L.cap_dpocon_work_size(n)), 1))
+    ok(r.call("dpocon", L.cap_dpocon, U, n, R, n, an_, rc_, W, r.stream), "cap_dpocon")
+    shim.hipFree(W)
+    for nrhs in (1, 17):
+        W = dmalloc(8 * max(int(L.cap_dpoerr_work_size(n, nrhs)), 1))
+        ok(r.call("dpoerr nrhs=%d" % nrhs, L.cap_dpoerr, U, n, nrhs, A, n, R, n, B, n, X, n, fe_, be_, W, r.stream), "cap_dpoerr")
+        shim.hipFree(W)
+    for (nrhs, absolute, beta) in ((3, 0, 0.0), (17, 1, 1.0)):
+        W = dmalloc(8 * max(int(L.cap_dsymm_thin_work_size(n, nrhs)), 1))
+        ok(r.call("dsymm_thin nrhs=%d" % nrhs, L.cap_dsymm_thin, U, absolute, n, nrhs, -1.0, A, n, X, n, beta, B, n, Y, n, W, r.stream), "cap_dsymm_thin")
+        shim.hipFree(W)
+    for q in (A, R, Cc, B, X, Y, small, piv):
+        shim.hipFree(q)
+
+
+def batched_case(r, n, batch=37, nrhs=19):
+    """the four batched entries: n <= 64 is the kernel of cap_dpotrf_batched behind either name, 64 < n <= 256 the blocked one"""
+    lda = n + 1
+    A = dmalloc(8 * lda * n * batch); B = dmalloc(8 * lda * nrhs * batch); info = dmalloc(4 * batch); ldet = dmalloc(8 * batch)
+    if n <= 64:
+        ok(r.call("dpotrf_batched", L.cap_dpotrf_batched, 1, n, A, lda, lda * n, batch, info, ldet, r.stream), "cap_dpotrf_batched")
+        ok(r.call("dpotrs_batched", L.cap_dpotrs_batched, 1, n, nrhs, A, lda, lda * n, B, lda, lda * nrhs, batch, info, r.stream), "cap_dpotrs_batched")
+    ok(r.call("dpotrf_batched_blocked", L.cap_dpotrf_batched_blocked, 1, n, A, lda, lda * n, batch, info, ldet, r.stream), "cap_dpotrf_batched_blocked")
+    ok(r.call("dpotrs_batched_blocked", L.cap_dpotrs_batched_blocked, 1, n, nrhs, A, lda, lda * n, B, lda, lda * nrhs, batch, info, r.stream),
+       "cap_dpotrs_batched_blocked")
+    for q in (A, B, info, ldet):
+        shim.hipFree(q)
+
+
+def cqr_kernels_case(r):
+    """Q^T B at the three widths of right-hand sides (one chunk of the streaming kernel, three chunks, the tile kernels beyond 48), a ragged
+    shape that the tile kernels take, and the two n = 256 sweep kernels on their own"""
+    m, n = 8192, 256
+    Q = dmalloc(8 * m * n); B = dmalloc(8 * m * 100); Z = dmalloc(8 * n * 100); G = dmalloc(8 * (n + 1) * n); Qo = dmalloc(8 * m * n)
+    for (mm, nn, nrhs) in ((m, n, 8), (m, n, 40), (m, n, 100), (5000, 37, 8)):
+        W = dmalloc(8 * max(int(L.cap_dgemm_tall_tn_work_size(mm, nn, nrhs)), 1))
+        ok(r.call("dgemm_tall_tn %dx%d nrhs=%d" % (mm, nn, nrhs), L.cap_dgemm_tall_tn, mm, nn, nrhs, Q, mm, B, mm, Z, nn, W, r.stream), "cap_dgemm_tall_tn")
+        shim.hipFree(W)
+    W = dmalloc(8 * max(int(L.cap_dgram256_work_size(m)), 1))
+    ok(r.call("dgram256", L.cap_dgram256, m, Q, m, G, n, W, 0, r.stream), "cap_dgram256")
+    ok(r.call("dgram256 max_wgs=3", L.cap_dgram256, m, Q, m, G, n + 1, W, 3, r.stream), "cap_dgram256")
+    ok(r.call("dqrapply256", L.cap_dqrapply256, m, Q, m, G, Qo, m, 0, r.stream), "cap_dqrapply256")
+    ok(r.call("dqrapply256 in place", L.cap_dqrapply256, m, Q, m, G, Q, m, 5, r.stream), "cap_dqrapply256")
+    for q in (Q, B, Z, G, W, Qo):
+        shim.hipFree(q)
 
 
 def group_of(color_of, key_of, size, rank):
@@ -641,6 +779,21 @@ def main(out_path, user_streams=(0, 1)):
             for p in range(P):
                 scenario("cacqr m=%d n=%d iter=%d P=%d rank=%d" % (m, n, iters, P, p), us, "cacqr m=%d n=%d iter=%d P=%d" % (m, n, iters, P), p, P)(
                     lambda r, a=(m, n, iters, P, p): cacqr_case(r, *a))
+        # ---- round 20: the entries written since round 6, none of which had a replay scenario.  Plan SEQUENCES without a host
+        # synchronisation between the calls (the shared block inverses, first-use scratch and helper streams of a cholinv plan; the
+        # slab buffer and block inverses of a CholeskyQR plan) and the plan-less entries at the sizes that reach each launch route
+        for (n, ci, opts) in [(2048, -1, (("nb", 256),)), (2048, -1, (("nb", 256), ("chud_kernel", 0))), (2048, -1, (("nb", 256), ("solve_kernel", 0))),
+                              (4096, -1, ()), (1000, -1, (("nb", 128),)),
+                              (2048, 0, (("nb", 256),)), (2048, 1, (("nb", 256),)), (2048, 1, (("nb", 256), ("solve_kernel", 0))),
+                              (2048, 0, (("nb", 256), ("solve_kernel", 0))), (3000, 1, ())]:
+            scenario("cholinv sequence n=%d ci=%d %s" % (n, ci, dict(opts) or ""), us)(lambda r, a=(n, ci, opts): cholinv_sequence_case(r, *a))
+        for n in (64, 200, 1000, 2048):
+            scenario("lapack extras n=%d" % n, us)(lambda r, a=n: lapack_extras_case(r, a))
+        for n in (8, 33, 64, 65, 193, 256):
+            scenario("batched n=%d" % n, us)(lambda r, a=n: batched_case(r, a))
+        scenario("cqr kernels: tall Q^T B nrhs 8 / 40 / 100, gram256, qrapply256", us)(cqr_kernels_case)
+        for (m, n, iters) in [(16384, 256, 2), (16384, 256, 3), (16384, 256, 4), (5000, 37, 3), (8192, 128, 4), (4096, 64, 1)]:
+            scenario("cacqr solve m=%d n=%d iter=%d" % (m, n, iters), us)(lambda r, a=(m, n, iters): cacqr_solve_case(r, *a))
     if 0 in user_streams:
         # ---- the CBLAS / LAPACKE offload library (always on the NULL stream): potrf at a size with look-ahead on helper streams, ragged products
         for (what, m, n, k) in [("dpotrf", 0, 5000, 0), ("dpotrf", 0, 1000, 0), ("dgemm", 3000, 2000, 1000), ("dgemm", 129, 77, 33), ("dgemm", 4096, 4, 4096),

@@ -77,9 +77,16 @@ def scenarios(per_mode):
     return {"results": per_mode["0"]["results"] + per_mode["1"]["results"]}
 
 
+# the entries that had no replay scenario before round 20
+ROUND20_ENTRIES = ("cap_cholinv_solve", "cap_cholinv_inverse", "cap_cholinv_logdet", "cap_cholinv_update", "cap_cholinv_rcond", "cap_cholinv_error_bounds",
+                   "cap_dpotrs", "cap_dpotri", "cap_dlauum", "cap_dcholupdate", "cap_dpstrf", "cap_dpocon", "cap_dpoerr", "cap_dlansy", "cap_dsymm_thin",
+                   "cap_dpotrf_batched", "cap_dpotrs_batched", "cap_dpotrf_batched_blocked", "cap_dpotrs_batched_blocked",
+                   "cap_dgemm_tall_tn", "cap_cacqr_solve", "cap_cacqr_apply_qt", "cap_cacqr_shift", "cap_dgram256", "cap_dqrapply256")
+
+
 def test_every_schedule_joins_its_streams_and_stays_inside_its_buffers(scenarios):
     res = scenarios["results"]
-    assert len(res) >= 1100, len(res)
+    assert len(res) >= 1180, len(res)
     bad = [(x["name"], x["findings"][:4]) for x in res if x["findings"]]
     assert not bad, "\n".join("%s: %s" % b for b in bad[:20])
     tot, unannotated = {}, {}
@@ -89,31 +96,50 @@ def test_every_schedule_joins_its_streams_and_stays_inside_its_buffers(scenarios
                 tot[k] = tot.get(k, 0) + v
         unannotated.update(x["stats"].get("unannotated", {}))
     # the scenarios really ran the schedules: tens of thousands of launches, event edges and collectives went through the stand-in
-    assert tot["kernels"] > 50000 and tot["waits"] > 50000 and tot["records"] > 50000 and tot["ops"] > 10000 and tot["oob"] == 0, tot
+    assert tot["kernels"] > 390000 and tot["waits"] > 460000 and tot["records"] > 370000 and tot["ops"] > 170000 and tot["oob"] == 0, tot
     # ... every launch came with its access notes, and millions of pairs of unordered operations were compared window by window
     assert not unannotated, unannotated
-    assert tot["accesses"] > 2000000 and tot["race_checks"] > 10000000 and tot["races"] == 0, tot
+    assert tot["accesses"] > 2400000 and tot["race_checks"] > 13000000 and tot["races"] == 0, tot
     # ... the ranks of every multi-rank configuration were replayed together, collective by collective
     joint = [x for x in res if "joint replay" in x["name"]]
-    assert len(joint) >= 120 and tot["collectives"] > 60000, (len(joint), tot)
+    assert len(joint) >= 122 and tot["collectives"] > 86000, (len(joint), tot)
     names = " ".join(x["name"] for x in res)
     for must in ("dist n=65536 nb=512 P=8  ci=-1 [joint replay of 8 ranks", "dist2d n=65536 nb=512 2x4  [joint replay of 8 ranks",
                  "dist n=8192 nb=512 P=8 {'ipc': 1} [joint replay of 8 ranks", "dist2d n=4096 nb=128 2x4 {'ipc': 1} [joint replay of 8 ranks",
                  "dmp n=8192 nb=512 P=8 [joint replay", "summa size=27 c=3 270x270x270 chunks=0 [joint replay of 27 ranks", "cholinv n=65536", "dist n=65536 nb=512 P=8 rank=7", "dist2d n=65536 nb=512 2x4 at (1,3)", "mpchol n=65536", "dmp n=8192 nb=512 P=8",
                  "cacqr m=2097152 n=256 iter=2 P=8", "cyclic_c=2", "{'ipc': 1}", "summa size=27 c=3 rank=26", "cacqr grid size=16 c=2 rank=15",
                  "redist n=1000 nb=128 size=8 c=2 Pr=2 rank=7", "desc n=300 nb=128 2x4 at (1,3)", "desc n=6144 nb=512 1x1",
-                 "dist2d n=4096 nb=128 4x4 {'ipc': 1} [joint replay of 16 ranks", "dist2d n=1152 nb=128 4x8  [joint replay of 32 ranks", "operators m=1000 n=777 k=515", "plan life cycles"):
+                 "dist2d n=4096 nb=128 4x4 {'ipc': 1} [joint replay of 16 ranks", "dist2d n=1152 nb=128 4x8  [joint replay of 32 ranks", "operators m=1000 n=777 k=515", "plan life cycles",
+                 # round 20: the entries written since round 6 - plan sequences without a host synchronisation between the calls, the plan-less
+                 # LAPACK-style entries, the batched entries, the tall-skinny product and the n = 256 sweep kernels, CholeskyQR's least squares
+                 "cholinv sequence n=2048 ci=-1 {'nb': 256}", "cholinv sequence n=2048 ci=-1 {'nb': 256, 'chud_kernel': 0}",
+                 "cholinv sequence n=2048 ci=-1 {'nb': 256, 'solve_kernel': 0}", "cholinv sequence n=4096 ci=-1", "cholinv sequence n=2048 ci=0 {'nb': 256}",
+                 "cholinv sequence n=2048 ci=1 {'nb': 256}", "cholinv sequence n=2048 ci=1 {'nb': 256, 'solve_kernel': 0}", "cholinv sequence n=3000 ci=1",
+                 "lapack extras n=64", "lapack extras n=2048", "batched n=8", "batched n=64", "batched n=65", "batched n=256", "cqr kernels: tall Q^T B nrhs 8 / 40 / 100",
+                 "cacqr solve m=16384 n=256 iter=2", "cacqr solve m=16384 n=256 iter=3", "cacqr solve m=16384 n=256 iter=4", "cacqr solve m=5000 n=37 iter=3"):
         assert must in names, must
+    # ... every entry of that list is CALLED (Run.call: marked, so that the join into the caller's stream is checked per call) with the
+    # caller on the NULL stream and on a non-blocking stream of its own
+    for mode in ("[NULL stream]", "[user stream]"):
+        called = set()
+        for x in res:
+            if mode in x["name"]:
+                called.update(x.get("entries", ()))
+        missing = [e for e in ROUND20_ENTRIES if e not in called]
+        assert not missing, (mode, missing)
 
 
 def test_plans_give_back_what_they_allocate(per_mode):
-    """Caller on the NULL stream: after 450+ plans / bundles / descriptors were created, used and destroyed the process holds what is
+    """Caller on the NULL stream: after 590+ plans / bundles / descriptors were created, used and destroyed the process holds what is
     per PROCESS by design - the chain's fall-back counters, the counter words + backup of the NULL stream and of the panel stream
     cap_dpotrf keeps per device, the NULL stream's split-K scratch - and nothing per plan."""
     d = per_mode["0"]
-    assert len(d["results"]) >= 450 and not any(x["findings"] for x in d["results"])
+    assert len(d["results"]) >= 590 and not any(x["findings"] for x in d["results"])
     live = d["live_allocations_at_exit"]
-    assert len(live) <= 6, live
+    # (round 20: the scenarios now reach cap_cholinv_solve / cap_dpotrs and cap_cholinv_update / cap_dcholupdate, whose give-up and injection
+    #  words - 16 bytes per device, potrs.hip and cholupdate.hip - are per process by design as well: two more words, nothing else)
+    words = [l for l in live if l.startswith("16 bytes")]
+    assert len(live) <= 8 and len(live) - len(words) <= 3, live
 
 
 def _lines(text):
