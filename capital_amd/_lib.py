@@ -35,6 +35,8 @@ SIGNATURES = {
     "cap_dpotrs_batched": (cint, [cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
     "cap_dpotrf_batched_blocked": (cint, [cint, i64, ptr, i64, i64, i64, ptr, ptr, ptr]),
     "cap_dpotrs_batched_blocked": (cint, [cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
+    "cap_dtrtri_batched": (cint, [cint, i64, ptr, i64, i64, i64, ptr, ptr]),
+    "cap_dpotri_batched": (cint, [cint, i64, ptr, i64, i64, i64, ptr, cint, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

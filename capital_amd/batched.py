@@ -1,8 +1,10 @@
-"""Many small SPD systems of one size on plain torch tensors: one launch factors (potrf) or solves (potrs) the whole batch.
+"""Many small SPD systems of one size on plain torch tensors: one launch factors (potrf), solves (potrs) or inverts (potri, trtri) the
+whole batch.
 
 The tensors are the memory the C ABI works on: fp64, on the device, n <= 256 (n <= 64: cap_dpotrf_batched / cap_dpotrs_batched,
 csrc/potrf_batched.hip, a wavefront per block; 64 < n <= 256: cap_dpotrf_batched_blocked / cap_dpotrs_batched_blocked,
-csrc/potrf_batched_blocked.hip, a workgroup per block).
+csrc/potrf_batched_blocked.hip, a workgroup per block; the inverses: cap_dtrtri_batched / cap_dpotri_batched, csrc/potri_batched.hip, one
+entry each for the whole range).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import torch
 
@@ -10,6 +12,8 @@ from . import _lib, lapack
 
 _PACK_F = lapack.ArgPack_potrf_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_S = lapack.ArgPack_potrs_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_T = lapack.ArgPack_trtri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_I = lapack.ArgPack_potri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 
 
 def _check(t, name, dims):
@@ -70,3 +74,35 @@ def potrs(R, B, info=None):
         raise _lib.CapitalError("R and B live on different devices")
     lapack.engine._potrs_batched(R, B3, n, nrhs, ldr, stride_r, ldb, max(stride_b, 0), batch, info, _PACK_S)
     return B
+
+
+def _info(info, T):
+    if info is not None and isinstance(info, torch.Tensor) and info.is_cuda and info.device != T.device:
+        raise _lib.CapitalError("info lives on another device")
+    return info
+
+
+def trtri(T, info=None):
+    """Triangular inverses of the batch, in place.  T: fp64 device tensor of shape (batch, n, n), n <= 256, under potrf's layout rules
+    (stride(2) == 1, stride(1) >= n, stride(0) >= n stride(1)).  Each T[i] is read as COLUMN-MAJOR memory and the upper triangle of that
+    column-major block is replaced by the upper triangle of its inverse (non-unit diagonal).  In torch's row-major reading of the same memory:
+    the LOWER triangle of T[i] holds L (for instance what potrf left there) and afterwards L^-1 = torch.linalg.inv(L); what torch reads as
+    the strictly upper triangle is neither read nor written.  A zero on the diagonal is not detected: it shows as infinities and NaNs inside
+    its own block.  info: what potrf returned, or None - a block with info != 0 gets NaN in that triangle.
+    Returns T.  Asynchronous on the current stream."""
+    batch, n, ld, stride = _blocks(T, "T")
+    lapack.engine._trtri_batched(T, n, ld, stride, batch, _info(info, T), _PACK_T)
+    return T
+
+
+def potri(R, info=None, symmetric=False):
+    """Inverses of the SPD blocks from the factors potrf left in R, in place (same layout rules as potrf's A; n <= 256).  The upper triangle
+    of each column-major block R[i] is replaced by that of A[i]^-1 = R^-1 R^-T.  In torch's row-major reading of the same memory: after
+    potrf(A); potri(A) the LOWER triangle of A[i] holds that of torch.cholesky_inverse(L) with L = torch.linalg.cholesky(A)[i], and what
+    torch reads as the strictly upper triangle is untouched.  With symmetric=True (the C ABI's fill = 1) A[i] holds the whole symmetric
+    inverse: the other triangle is the bit-identical mirror, copied and never computed a second time.
+    info: what potrf returned, or None - a block with info != 0 gets NaN wherever the call writes (the triangle, or the whole block with
+    symmetric=True).  Returns R.  Asynchronous on the current stream."""
+    batch, n, ld, stride = _blocks(R, "R")
+    lapack.engine._potri_batched(R, n, ld, stride, batch, _info(info, R), _PACK_I, fill=bool(symmetric))
+    return R

@@ -2,8 +2,9 @@
 
 _potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor), _cholupdate (that factor after A +- V V^T), _pstrf (the
 pivoted factorization of a semidefinite A, LAPACK's dpstrf), _lansy (the 1-norm of a symmetric matrix), _pocon (the reciprocal condition
-number from the factor, LAPACK's dpocon), _poerr (the error bounds of LAPACK's dporfs) and _potrf_batched / _potrs_batched (the factor and
-solve of many small blocks of one size in one launch) have no counterpart upstream.
+number from the factor, LAPACK's dpocon), _poerr (the error bounds of LAPACK's dporfs) and _potrf_batched / _potrs_batched / _trtri_batched /
+_potri_batched (the factor, solve, triangular inverse and SPD inverse of many small blocks of one size in one launch) have no counterpart
+upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -43,6 +44,8 @@ class Method(enum.IntEnum):
     AlapackPoerr = 0x8          # extension: not in the reference's enum
     AlapackPotrfBatched = 0x9   # extension: not in the reference's enum
     AlapackPotrsBatched = 0xA   # extension: not in the reference's enum
+    AlapackTrtriBatched = 0xB   # extension: not in the reference's enum
+    AlapackPotriBatched = 0xC   # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
 
@@ -104,6 +107,18 @@ class ArgPack_potrf_batched:
 class ArgPack_potrs_batched:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPotrsBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_trtri_batched:
+    def __init__(self, order, uplo, diag=Diag.AlapackNonUnit):
+        self.method = Method.AlapackTrtriBatched
+        self.order, self.uplo, self.diag = Order(order), UpLo(uplo), Diag(diag)
+
+
+class ArgPack_potri_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotriBatched
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -265,6 +280,40 @@ class engine:
         st = fn(int(srcPackage.uplo), n, nrhs, dptr(matrixR), ldr, stride_r, dptr(matrixB), ldb, stride_b, batch,
                 info.data_ptr() if info is not None else None, cur_stream(stream))
         _lib.check(st, "lapack::engine::_potrs_batched")
+
+    @staticmethod
+    def _batched_info(info, batch):
+        if info is not None and (not isinstance(info, torch.Tensor) or not info.is_cuda or info.dtype != torch.int32
+                                 or info.numel() < batch or not info.is_contiguous()):
+            raise _lib.CapitalError("info must be a contiguous int32 device tensor of batch entries")
+        return info.data_ptr() if info is not None else None
+
+    @staticmethod
+    def _trtri_batched(matrixT, n, ldt, stride, batch, info, srcPackage, stream=None):
+        """The upper triangles of the n x n blocks (n <= 256, column-major, ld ldt) at matrixT + i stride, i < batch, <- those of their inverses
+        (non-unit diagonal), in place, in one launch (cap_dtrtri_batched: n <= 64 a wavefront per block, 64 < n <= 256 a workgroup per block).
+        info: what _potrf_batched returned, or None; a block with info != 0 gets NaN in its upper triangle.  A zero on a diagonal is not
+        detected.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor or getattr(srcPackage, "diag", Diag.AlapackNonUnit) != Diag.AlapackNonUnit:
+            raise _lib.CapitalError("only AlapackColumnMajor / AlapackNonUnit is supported")
+        _batched_blocked(None, n)
+        L = _lib.lib()
+        st = L.cap_dtrtri_batched(int(srcPackage.uplo), n, dptr(matrixT), ldt, stride, batch, engine._batched_info(info, batch), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_trtri_batched")
+
+    @staticmethod
+    def _potri_batched(matrixR, n, ldr, stride, batch, info, srcPackage, fill=False, stream=None):
+        """The upper triangles of the n x n blocks (n <= 256, column-major, ld ldr) at matrixR + i stride, i < batch - the factors R_i
+        _potrf_batched left - <- those of A_i^-1 = R_i^-1 R_i^-T, in place, in one launch (cap_dpotri_batched).  fill: the strictly lower
+        triangles become the bit-identical mirrors of the upper ones.  info: what _potrf_batched returned, or None; a block with info != 0
+        gets NaN wherever the call writes.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        _batched_blocked(None, n)
+        L = _lib.lib()
+        st = L.cap_dpotri_batched(int(srcPackage.uplo), n, dptr(matrixR), ldr, stride, batch, engine._batched_info(info, batch),
+                                  1 if fill else 0, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potri_batched")
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

@@ -209,6 +209,28 @@ int cap_dpotrf_batched_blocked(int uplo, int64_t n, double* A, int64_t lda, int6
 int cap_dpotrs_batched_blocked(int uplo, int64_t n, int64_t nrhs, const double* R, int64_t ldr, int64_t stride_r, double* B, int64_t ldb,
                                int64_t stride_b, int64_t batch, const int* info, void* stream);
 
+/* Batched triangular inverse and SPD inverse from the factor (csrc/potri_batched.hip): block i is the n x n column-major block at
+ * T + i * stride_t (R + i * stride_r) with the given leading dimension, 1 <= n <= 256, fp64, upper, one GPU.  One entry per operation for
+ * the whole range: n <= 64 runs one wavefront per 64 / NP blocks (NP = 8, 16, 32 or 64 >= n), 64 < n <= 256 one workgroup per block.
+ * The contract is that of the batched entries above: ONE launch per call on a 1-D grid, no `work` argument, no allocation, no memset, no
+ * atomics, no mutex, no helper stream, no host synchronisation; asynchronous on `stream`, callable from several host threads; 64-bit
+ * offsets; divisions are correctly rounded, no reciprocal estimates; a block's bits depend on (n, its own data, fill) alone - not on its
+ * position in the batch, the batch size, ld / stride or alignment (all global accesses are 8-byte ones: one load path).
+ * cap_dtrtri_batched: the upper triangle of every block <- that of T_i^-1 (non-unit diagonal).  A zero on the diagonal is not detected: it
+ * propagates as IEEE infinities and NaNs inside its own block only (cap_dtrtri has no info either).
+ * cap_dpotri_batched: R holds the factors cap_dpotrf_batched[_blocked] left; the upper triangle of every block <- that of A_i^-1 =
+ * R_i^-1 R_i^-T.  fill = 0: the upper triangle only; fill = 1: the strictly lower triangle becomes the bit-identical mirror of the upper one
+ * (copied, never computed a second time), cap_cholinv_inverse's fill; any other fill -> CAP_ERR_ARG.
+ * info (what the factor call wrote, may be NULL): a block with info[i] != 0 gets NaN in everything the call would have written for it (the
+ * upper triangle, or the n x n window with fill = 1) and its input is not interpreted - the convention of cap_dpotrs_batched.
+ * Never read: the strictly lower triangle of an input block, rows n .. ld - 1 of every column, the gaps between blocks, everything behind
+ * the last block.  Never written: the same elements, except the strictly lower triangle under fill = 1.
+ * Argument rules, in this order, all decided before any device call: n < 0, batch < 0, a NULL block pointer with n batch > 0, ld < n,
+ * batch > 1 with stride < ld n, a bad fill -> CAP_ERR_ARG; uplo = LOWER -> CAP_ERR_UNSUPPORTED; n > 256 -> CAP_ERR_UNSUPPORTED (also for an
+ * empty batch); 64 < n with a batch beyond one grid dimension -> CAP_ERR_UNSUPPORTED; n == 0 or batch == 0 -> CAP_OK without a launch.   */
+int cap_dtrtri_batched(int uplo, int64_t n, double* T, int64_t ldt, int64_t stride_t, int64_t batch, const int* info, void* stream);
+int cap_dpotri_batched(int uplo, int64_t n, double* R, int64_t ldr, int64_t stride_r, int64_t batch, const int* info, int fill, void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
