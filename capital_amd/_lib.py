@@ -37,6 +37,13 @@ SIGNATURES = {
     "cap_dpotrs_batched_blocked": (cint, [cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
     "cap_dtrtri_batched": (cint, [cint, i64, ptr, i64, i64, i64, ptr, ptr]),
     "cap_dpotri_batched": (cint, [cint, i64, ptr, i64, i64, i64, ptr, cint, ptr]),
+    "cap_vbatch_plan_create": (cint, [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(ptr)]),
+    "cap_vbatch_plan_destroy": (cint, [ptr]),
+    "cap_vbatch_plan_info": (i64, [ptr, cint]),
+    "cap_vbatch_plan_table": (cint, [ptr, cint, C.POINTER(i64), i64]),
+    "cap_dpotrf_vbatched": (cint, [ptr, cint, ptr, ptr, ptr, ptr]),
+    "cap_dpotrs_vbatched": (cint, [ptr, cint, i64, ptr, ptr, i64, ptr, ptr]),
+    "cap_dpotri_vbatched": (cint, [ptr, cint, ptr, ptr, cint, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

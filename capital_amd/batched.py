@@ -5,7 +5,11 @@ The tensors are the memory the C ABI works on: fp64, on the device, n <= 256 (n 
 csrc/potrf_batched.hip, a wavefront per block; 64 < n <= 256: cap_dpotrf_batched_blocked / cap_dpotrs_batched_blocked,
 csrc/potrf_batched_blocked.hip, a workgroup per block; the inverses: cap_dtrtri_batched / cap_dpotri_batched, csrc/potri_batched.hip, one
 entry each for the whole range).
+Blocks of DIFFERENT sizes: VarBatch, a plan built once from host-side sizes (cap_vbatch_plan, csrc/potrf_vbatched.hip), whose potrf / potrs /
+potri take one launch per size class that occurs.
 There is no CPU path and no fallback: anything else raises CapitalError."""
+import ctypes
+
 import torch
 
 from . import _lib, lapack
@@ -14,6 +18,9 @@ _PACK_F = lapack.ArgPack_potrf_batched(lapack.Order.AlapackColumnMajor, lapack.U
 _PACK_S = lapack.ArgPack_potrs_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_T = lapack.ArgPack_trtri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_I = lapack.ArgPack_potri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VF = lapack.ArgPack_potrf_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VS = lapack.ArgPack_potrs_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VI = lapack.ArgPack_potri_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 
 
 def _check(t, name, dims):
@@ -106,3 +113,120 @@ def potri(R, info=None, symmetric=False):
     batch, n, ld, stride = _blocks(R, "R")
     lapack.engine._potri_batched(R, n, ld, stride, batch, _info(info, R), _PACK_I, fill=bool(symmetric))
     return R
+
+
+class VarBatch:
+    """A batch of SPD blocks of DIFFERENT sizes 0 <= n_i <= 256 inside ONE flat fp64 device tensor: block i is the n_i x n_i column-major block
+    at element offsets[i] with leading dimension ld[i].  sizes, ld, offsets: host sequences of ints; ld=None: ld[i] = max(n_i, 1);
+    offsets=None: the blocks lie back to back in batch order.  The plan (cap_vbatch_plan) sorts the blocks once into the size classes of the
+    fixed-size kernels and lives on the device that is current when it is made; building and freeing it may synchronise, no other method
+    does.  It is reusable for any number of calls, from several streams at once.  Every block gets, bit for bit, what the fixed-size
+    functions of this module give for it alone - whichever blocks travel with it.
+    .offsets / .row_offsets: tuples in batch order (row_offsets: the prefix sum of the sizes - the rows of the stacked right-hand sides);
+    .total: elements the blocks span (the least length of A); .rows: sum of the sizes; .launches: launches per call.
+    Overlapping blocks, negative sizes, ld[i] < n_i or a size above 256 raise CapitalError."""
+
+    def __init__(self, sizes, ld=None, offsets=None):
+        self.sizes = tuple(int(x) for x in sizes)
+        batch = len(self.sizes)
+        for name, seq in (("ld", ld), ("offsets", offsets)):
+            if seq is not None and len(seq) != batch:
+                raise _lib.CapitalError("%s must have one entry per block (%d), got %d" % (name, batch, len(seq)))
+        arr = lambda seq: (ctypes.c_int64 * max(batch, 1))(*[int(x) for x in seq]) if seq is not None else None
+        L = _lib.lib()
+        self._L, self._plan = L, ctypes.c_void_p()
+        _lib.check(L.cap_vbatch_plan_create(batch, arr(self.sizes), arr(ld), arr(offsets), ctypes.byref(self._plan)), "VarBatch")
+        self.batch = batch
+        self.ld = tuple(int(x) for x in ld) if ld is not None else tuple(max(n, 1) for n in self.sizes)
+        if offsets is not None:
+            self.offsets = tuple(int(x) for x in offsets)
+        else:
+            self.offsets, at = [], 0
+            for n, l in zip(self.sizes, self.ld):
+                self.offsets.append(at)
+                at += l * n
+            self.offsets = tuple(self.offsets)
+        rows, at = [], 0
+        for n in self.sizes:
+            rows.append(at)
+            at += n
+        self.row_offsets = tuple(rows)
+        self.total = int(L.cap_vbatch_plan_info(self._plan, 1))
+        self.rows = int(L.cap_vbatch_plan_info(self._plan, 2))
+        self.launches = int(L.cap_vbatch_plan_info(self._plan, 4))
+        self.device = torch.cuda.current_device() if torch.cuda.is_available() else None
+
+    def __del__(self):
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            self._L.cap_vbatch_plan_destroy(plan)
+
+    def _flat(self, A, name):
+        _check(A, name, (1,))
+        if A.numel() < self.total or (A.numel() > 1 and A.stride(0) != 1):
+            raise _lib.CapitalError("%s must be a contiguous 1-D tensor of at least %d elements, got shape %s, strides %s"
+                                    % (name, self.total, tuple(A.shape), A.stride()))
+        if A.device.index != self.device:
+            raise _lib.CapitalError("%s lives on device %s, the plan on device %s" % (name, A.device.index, self.device))
+        return A
+
+    def potrf(self, A, logdet=False):
+        """Cholesky factors of all blocks, in place.  A: 1-D fp64 device tensor of at least .total elements.  The upper triangle of every
+        column-major block <- R_i (A_i = R_i^T R_i); in torch's row-major reading of the same memory (.block) the LOWER triangle then holds
+        L = torch.linalg.cholesky(A_i).  Strictly lower triangles, padding rows and gaps are neither read nor written.
+        Returns info (int32, batch order: 0, or the 1-based first pivot that is not > 0 - that block holds NaN from that row of R on; 0
+        for an empty block), or (info, logdet) with logdet=True.  Asynchronous on the current stream."""
+        info, ld = lapack.engine._potrf_vbatched(self._plan, self._flat(A, "A"), self.batch, _PACK_VF, want_logdet=bool(logdet))
+        return (info, ld) if logdet else info
+
+    def potrs(self, R, B, info=None):
+        """Solves A_i x = b_i for all blocks in place with the factors potrf left in R.  B: fp64 device tensor of shape (rows,) or (nrhs, rows)
+        with stride(-1) == 1 - every right-hand side is the stacked vector, block i owning entries row_offsets[i] .. row_offsets[i] + n_i: the
+        call applies the inverse of the block-diagonal matrix.  info: what potrf returned, or None - a block with info != 0 gets NaN.
+        Returns B.  Asynchronous on the current stream."""
+        self._flat(R, "R")
+        _check(B, "B", (1, 2))
+        B2 = B.unsqueeze(0) if B.dim() == 1 else B
+        if B2.shape[1] != self.rows:
+            raise _lib.CapitalError("B must be (rows,) or (nrhs, rows) with rows = %d, got shape %s" % (self.rows, tuple(B.shape)))
+        nrhs = B2.shape[0]
+        if self.rows > 1 and B2.stride(1) != 1:
+            raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
+        ldb = B2.stride(0) if nrhs > 1 else max(self.rows, 1)
+        if ldb < self.rows:
+            raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
+        if B.device != R.device:
+            raise _lib.CapitalError("R and B live on different devices")
+        lapack.engine._potrs_vbatched(self._plan, R, B2, nrhs, ldb, self.batch, _info(info, R), _PACK_VS)
+        return B
+
+    def potri(self, R, info=None, symmetric=False):
+        """Inverses of the SPD blocks from the factors potrf left in R, in place: the upper triangle of every column-major block <- that of
+        A_i^-1; in torch's row-major reading (.block) the LOWER triangle holds that of torch.cholesky_inverse(L).  symmetric=True: the
+        other triangle becomes the bit-identical mirror.  info: what potrf returned, or None - a block with info != 0 gets NaN wherever the
+        call writes.  Returns R.  Asynchronous on the current stream."""
+        lapack.engine._potri_vbatched(self._plan, self._flat(R, "R"), self.batch, _info(info, R), _PACK_VI, fill=bool(symmetric))
+        return R
+
+    def block(self, A, i):
+        """The n_i x n_i view of block i of the flat tensor A in torch's row-major reading: block(A, i)[r, c] is element (c, r) of the
+        column-major block, so after potrf torch sees L (lower triangular, L L^T = A_i) in the LOWER triangle of the view, as in potrf
+        of this module."""
+        n = self.sizes[i]
+        return A.as_strided((n, n), (self.ld[i], 1), A.storage_offset() + self.offsets[i])
+
+    def pack(self, blocks, device=None):
+        """The flat fp64 device tensor (.total elements, zeros in padding and gaps) that holds blocks[i] (2-D, n_i x n_i, any dtype /
+        device) as block i in torch's reading: pack(bl) followed by block(., i) gives bl[i] back."""
+        if len(blocks) != self.batch:
+            raise _lib.CapitalError("pack needs one matrix per block (%d), got %d" % (self.batch, len(blocks)))
+        for i, b in enumerate(blocks):
+            if not isinstance(b, torch.Tensor) or tuple(b.shape) != (self.sizes[i], self.sizes[i]):
+                raise _lib.CapitalError("block %d must be a %d x %d tensor, got %s" % (i, self.sizes[i], self.sizes[i], tuple(getattr(b, "shape", ()))))
+        if device is None and self.device is None:
+            raise _lib.CapitalError("there is no device to pack to - there is no CPU path")
+        A = torch.zeros(max(self.total, 1), dtype=torch.float64, device=torch.device("cuda", self.device if device is None else device))
+        for i, b in enumerate(blocks):
+            if self.sizes[i]:
+                self.block(A, i).copy_(b)
+        return A[:self.total]

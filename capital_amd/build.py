@@ -22,7 +22,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 NO_SCRATCH = ("dgemm_tn_dma_kernel", "gram256_kernel", "qrapply256_kernel", "bf16_tn_kernel", "bf16_tn_v2_kernel", "bf16_tn3_kernel", "bf16_tn3w_kernel", "bf16_tn3x_kernel", "leaf_cholinv_kernel",
               "panel64_solve_update_kernel", "chain64_coop_kernel", "potrs_subst_kernel", "dlauum_nt_kernel", "tall_tn_kernel", "chud_sweep_kernel", "chud_step_kernel",
               "pstrf_step_kernel", "symm_thin_part_kernel", "symm_thin_reduce_kernel", "pocon_step_kernel", "pocon_init_kernel", "potrf_batched_kernel", "potrs_batched_kernel",
-              "potrf_batched_blocked_kernel", "potrs_batched_blocked_kernel", "potri_batched_kernel", "potri_batched_blocked_kernel")
+              "potrf_batched_blocked_kernel", "potrs_batched_blocked_kernel", "potri_batched_kernel", "potri_batched_blocked_kernel",
+              "potrf_vbatched_kernel", "potrs_vbatched_kernel", "potri_vbatched_kernel", "potrf_vbatched_blocked_kernel", "potrs_vbatched_blocked_kernel",
+              "potri_vbatched_blocked_kernel")
 
 
 def sources():

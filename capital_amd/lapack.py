@@ -3,8 +3,8 @@
 _potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor), _cholupdate (that factor after A +- V V^T), _pstrf (the
 pivoted factorization of a semidefinite A, LAPACK's dpstrf), _lansy (the 1-norm of a symmetric matrix), _pocon (the reciprocal condition
 number from the factor, LAPACK's dpocon), _poerr (the error bounds of LAPACK's dporfs) and _potrf_batched / _potrs_batched / _trtri_batched /
-_potri_batched (the factor, solve, triangular inverse and SPD inverse of many small blocks of one size in one launch) have no counterpart
-upstream.
+_potri_batched (the factor, solve, triangular inverse and SPD inverse of many small blocks of one size in one launch) and _potrf_vbatched /
+_potrs_vbatched / _potri_vbatched (the same for blocks of different sizes, described by a cap_vbatch_plan) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -46,6 +46,9 @@ class Method(enum.IntEnum):
     AlapackPotrsBatched = 0xA   # extension: not in the reference's enum
     AlapackTrtriBatched = 0xB   # extension: not in the reference's enum
     AlapackPotriBatched = 0xC   # extension: not in the reference's enum
+    AlapackPotrfVbatched = 0xD  # extension: not in the reference's enum
+    AlapackPotrsVbatched = 0xE  # extension: not in the reference's enum
+    AlapackPotriVbatched = 0xF  # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
 
@@ -119,6 +122,24 @@ class ArgPack_trtri_batched:
 class ArgPack_potri_batched:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPotriBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_potrf_vbatched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotrfVbatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_potrs_vbatched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotrsVbatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_potri_vbatched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotriVbatched
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -314,6 +335,46 @@ class engine:
         st = L.cap_dpotri_batched(int(srcPackage.uplo), n, dptr(matrixR), ldr, stride, batch, engine._batched_info(info, batch),
                                   1 if fill else 0, cur_stream(stream))
         _lib.check(st, "lapack::engine::_potri_batched")
+
+    @staticmethod
+    def _potrf_vbatched(plan, matrixA, batch, srcPackage, want_logdet=False, stream=None):
+        """The blocks of different sizes (n_i <= 256) that `plan` (a cap_vbatch_plan handle) describes inside matrixA <- their upper factors:
+        cap_dpotrf_vbatched, one launch per non-empty size class.  Returns (info, logdet) in batch order as _potrf_batched does; the entries of
+        empty blocks are 0.  Nothing is read back: asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        dev = matrixA.device if isinstance(matrixA, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        info = torch.zeros(max(batch, 1), dtype=torch.int32, device=dev)
+        logdet = torch.zeros(max(batch, 1), dtype=torch.float64, device=dev) if want_logdet else None
+        st = L.cap_dpotrf_vbatched(plan, int(srcPackage.uplo), dptr(matrixA), info.data_ptr(), logdet.data_ptr() if want_logdet else None,
+                                   cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrf_vbatched")
+        return info[:max(batch, 0)], (logdet[:max(batch, 0)] if want_logdet else None)
+
+    @staticmethod
+    def _potrs_vbatched(plan, matrixR, matrixB, nrhs, ldb, batch, info, srcPackage, stream=None):
+        """The stacked right-hand sides matrixB ((sum n_i) x nrhs, column-major, ld ldb; block i owns the rows behind the prefix sum of n) <-
+        the solutions with the factors _potrf_vbatched left in matrixR, n_i <= 256: cap_dpotrs_vbatched.  info: what _potrf_vbatched
+        returned, or None; a block with info != 0 gets NaN.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        st = L.cap_dpotrs_vbatched(plan, int(srcPackage.uplo), nrhs, dptr(matrixR), dptr(matrixB), ldb, engine._batched_info(info, batch),
+                                   cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrs_vbatched")
+
+    @staticmethod
+    def _potri_vbatched(plan, matrixR, batch, info, srcPackage, fill=False, stream=None):
+        """The upper triangles of the factors _potrf_vbatched left in matrixR (n_i <= 256) <- those of the inverses A_i^-1: cap_dpotri_vbatched.
+        fill: the strictly lower triangles become the bit-identical mirrors.  info: what _potrf_vbatched returned, or None; a block with
+        info != 0 gets NaN wherever the call writes.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        st = L.cap_dpotri_vbatched(plan, int(srcPackage.uplo), dptr(matrixR), engine._batched_info(info, batch), 1 if fill else 0,
+                                   cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potri_vbatched")
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

@@ -231,6 +231,47 @@ int cap_dpotrs_batched_blocked(int uplo, int64_t n, int64_t nrhs, const double* 
 int cap_dtrtri_batched(int uplo, int64_t n, double* T, int64_t ldt, int64_t stride_t, int64_t batch, const int* info, void* stream);
 int cap_dpotri_batched(int uplo, int64_t n, double* R, int64_t ldr, int64_t stride_r, int64_t batch, const int* info, int fill, void* stream);
 
+/* Variable-size batched Cholesky (potrf_vbatched of the vendor libraries; csrc/potrf_vbatched.hip): factor, solve and SPD inverse of a batch
+ * of blocks of DIFFERENT sizes 0 <= n_i <= 256 - fp64, upper, column-major - described once by a PLAN.
+ * cap_vbatch_plan_create: n, ld, offset are HOST arrays of `batch` entries; block i is the n_i x n_i block at A + offset[i] with leading
+ * dimension ld[i].  ld == NULL: ld[i] = max(n_i, 1); offset == NULL: the blocks lie back to back in batch order (offset[i] = sum_{j<i}
+ * ld[j] n_j).  Argument rules, in this order: NULL out, batch < 0, NULL n with batch > 0, some n_i < 0, ld[i] < n_i or offset[i] < 0, two
+ * non-empty blocks whose windows [offset, offset + (n - 1) ld + n) meet (checked after sorting the windows by offset; a block inside
+ * another one's padding counts) -> CAP_ERR_ARG; then some n_i > 256 -> CAP_ERR_UNSUPPORTED; then a size class with more blocks than one
+ * grid dimension serves -> CAP_ERR_UNSUPPORTED.  n_i = 0 is legal: nothing of that block is touched, info[i] and logdet[i] are NOT
+ * written (zero them once; the Python layer does).  batch = 0 is legal.
+ * Create sorts the blocks into seven size classes - NP = 8, 16, 32, 64 >= n_i (a wavefront per 64 / NP blocks) and NBLK = ceil(n_i / 64) =
+ * 2, 3, 4 (a workgroup per block) - each list stably sorted by n_i, builds the per-block records (offset, ld, row offset, n) and uploads
+ * both to the CURRENT device with synchronous copies: create and destroy MAY SYNCHRONISE the device and allocate / free device memory; no
+ * other call of this section does.  The plan is read-only afterwards: any number of calls, from several streams and host threads at once.
+ * In a process without a device create still succeeds and the plan serves cap_vbatch_plan_info / _table; the three entries return
+ * CAP_ERR_HIP for it unless there is nothing to launch.
+ * cap_vbatch_plan_info(p, what): CAP_VBATCH_BATCH; _TOTAL = elements spanned (the largest offset + (n - 1) ld + n); _ROWS = sum n_i;
+ * _NMAX = the largest n_i; _LAUNCHES = the number of non-empty classes = launches per call; _COUNT + c, c = 0 .. 6 = blocks of class c (in
+ * the order above).  -1 for a NULL plan or an unknown `what`.  cap_vbatch_plan_table(p, c, blocks, cap): the first min(cap, count) block
+ * indices of class c's list, a host copy; NULL plan, c outside 0 .. 6, cap < 0, NULL blocks with cap > 0 -> CAP_ERR_ARG.
+ * The three entries, asynchronous on `stream`: ONE launch per non-empty class (seven at most), all on `stream`; no scratch, no allocation,
+ * no memset, no atomics, no helper stream, no host synchronisation.  info (may be NULL) and logdet (may be NULL) have `batch` entries in
+ * BATCH order; their conventions, the NaN rows of a failed block, what is never read or written, and `fill` are those of
+ * cap_dpotrf_batched[_blocked] / cap_dpotrs_batched[_blocked] / cap_dpotri_batched.
+ * cap_dpotrs_vbatched: B is the STACKED system, (sum n_i) x nrhs column-major with ldb >= sum n_i; block i owns rows row_off[i] ..
+ * row_off[i] + n_i, row_off the prefix sum of n in batch order: the call applies the inverse of the block-diagonal matrix.  Any nrhs >= 0.
+ * THE BIT CONTRACT: for every block i the three entries write, bit for bit, what cap_dpotrf_batched_blocked / cap_dpotrs_batched_blocked /
+ * cap_dpotri_batched write on the same data with n = n_i and batch = 1 - info[i] and logdet[i] included - whichever blocks share its
+ * wavefront, its class list or the batch, and whatever ld[i], offset[i] and the order of the batch.
+ * Entry rules, in this order: NULL plan, nrhs < 0, a NULL A / R / B when something would be launched, ldb < sum n_i, fill other than 0 / 1
+ * -> CAP_ERR_ARG; uplo = LOWER -> CAP_ERR_UNSUPPORTED; an empty plan, an all-zero-size plan or nrhs = 0 -> CAP_OK without a launch.          */
+typedef struct cap_vbatch_plan cap_vbatch_plan;
+enum { CAP_VBATCH_BATCH = 0, CAP_VBATCH_TOTAL = 1, CAP_VBATCH_ROWS = 2, CAP_VBATCH_NMAX = 3, CAP_VBATCH_LAUNCHES = 4, CAP_VBATCH_COUNT = 5 };
+int cap_vbatch_plan_create(int64_t batch, const int64_t* n, const int64_t* ld, const int64_t* offset, cap_vbatch_plan** out);
+int cap_vbatch_plan_destroy(cap_vbatch_plan* p);
+int64_t cap_vbatch_plan_info(const cap_vbatch_plan* p, int what);
+int cap_vbatch_plan_table(const cap_vbatch_plan* p, int cls, int64_t* blocks, int64_t cap);
+int cap_dpotrf_vbatched(const cap_vbatch_plan* p, int uplo, double* A, int* info, double* logdet, void* stream);
+int cap_dpotrs_vbatched(const cap_vbatch_plan* p, int uplo, int64_t nrhs, const double* R, double* B, int64_t ldb, const int* info,
+                        void* stream);
+int cap_dpotri_vbatched(const cap_vbatch_plan* p, int uplo, double* R, const int* info, int fill, void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
