@@ -44,6 +44,8 @@ SIGNATURES = {
     "cap_dpotrf_vbatched": (cint, [ptr, cint, ptr, ptr, ptr, ptr]),
     "cap_dpotrs_vbatched": (cint, [ptr, cint, i64, ptr, ptr, i64, ptr, ptr]),
     "cap_dpotri_vbatched": (cint, [ptr, cint, ptr, ptr, cint, ptr]),
+    "cap_dcholupdate_batched": (cint, [cint, cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
+    "cap_dcholupdate_vbatched": (cint, [ptr, cint, cint, i64, ptr, ptr, i64, ptr, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

@@ -7,6 +7,8 @@ csrc/potrf_batched_blocked.hip, a workgroup per block; the inverses: cap_dtrtri_
 entry each for the whole range).
 Blocks of DIFFERENT sizes: VarBatch, a plan built once from host-side sizes (cap_vbatch_plan, csrc/potrf_vbatched.hip), whose potrf / potrs /
 potri take one launch per size class that occurs.
+update / downdate (and VarBatch.update / .downdate): the factors of A_i +- V_i V_i^T from those of A_i in place, one launch
+(cap_dcholupdate_batched / cap_dcholupdate_vbatched, csrc/cholupdate_batched.hip).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
@@ -21,6 +23,8 @@ _PACK_I = lapack.ArgPack_potri_batched(lapack.Order.AlapackColumnMajor, lapack.U
 _PACK_VF = lapack.ArgPack_potrf_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_VS = lapack.ArgPack_potrs_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_VI = lapack.ArgPack_potri_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_U = lapack.ArgPack_cholupdate_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VU = lapack.ArgPack_cholupdate_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 
 
 def _check(t, name, dims):
@@ -115,6 +119,59 @@ def potri(R, info=None, symmetric=False):
     return R
 
 
+def _own_info(info, batch, R):
+    """the info tensor of update / downdate: the caller's (checked), or a fresh zeroed one"""
+    if info is None:
+        return torch.zeros(max(batch, 1), dtype=torch.int32, device=R.device)[:batch]
+    if (not isinstance(info, torch.Tensor) or not info.is_cuda or info.dtype != torch.int32 or info.numel() < batch
+            or not info.is_contiguous()):
+        raise _lib.CapitalError("info must be a contiguous int32 device tensor of batch entries")
+    if info.device != R.device:
+        raise _lib.CapitalError("info lives on another device")
+    return info
+
+
+def _cholupdate(R, V, info, sign):
+    batch, n, ldr, stride_r = _blocks(R, "R")
+    _check(V, "V", (2, 3))
+    V3 = V.unsqueeze(1) if V.dim() == 2 else V
+    if V3.shape[0] != batch or V3.shape[2] != n:
+        raise _lib.CapitalError("V must be (batch, k, n) or (batch, n) with batch = %d, n = %d, got shape %s" % (batch, n, tuple(V.shape)))
+    k = V3.shape[1]
+    if n > 1 and V3.stride(2) != 1:
+        raise _lib.CapitalError("every column of V must be contiguous, got strides %s" % (V.stride(),))
+    ldv = V3.stride(1) if k > 1 else max(n, 1)
+    stride_v = V3.stride(0)
+    if ldv < n or (batch > 1 and stride_v < ldv * k):
+        raise _lib.CapitalError("V: columns overlap (strides %s)" % (V.stride(),))
+    if V.device != R.device:
+        raise _lib.CapitalError("R and V live on different devices")
+    info = _own_info(info, batch, R)
+    lapack.engine._cholupdate_batched(R, V3, n, k, ldr, stride_r, ldv, max(stride_v, 0), batch, sign, info if batch > 0 else None, _PACK_U)
+    return info
+
+
+def update(R, V, info=None):
+    """Rank-k update of the factors potrf left in R, in place: R[i] <- the factor of A[i] + V_i V_i^T (same layout rules as potrf's A,
+    n <= 256).  V: fp64 device tensor of shape (batch, k, n) or (batch, n) with stride(-1) == 1: V[i, q] is column q of V_i, every column
+    contiguous like the right-hand sides of potrs; V is not written.  Any k; more than 16 columns are further passes inside the one launch.
+    In torch's row-major reading of the same memory the LOWER triangle of R[i] holds L = torch.linalg.cholesky(A)[i] and afterwards L' with
+    L' L'^T = A[i] + V[i]^T V[i] (the sum of the outer products of the rows V[i, q]); what torch reads as the strictly upper triangle is
+    neither read nor written.
+    info: int32 device tensor of batch entries, read and written in place - a block with info != 0 (a failed potrf, an earlier failed
+    downdate) is not touched - or None for a fresh zeroed one.  Returns info.  Every block gets, bit for bit, what cap_dcholupdate gives
+    for it alone.  Asynchronous on the current stream; nothing is read back."""
+    return _cholupdate(R, V, info, 1)
+
+
+def downdate(R, V, info=None):
+    """Rank-k downdate, in place: R[i] <- the factor of A[i] - V_i V_i^T; R, V, info and the layout as in update.  In torch's row-major
+    reading the LOWER triangle of R[i] afterwards holds L' with L' L'^T = A[i] - V[i]^T V[i].  A block whose A[i] - V_i V_i^T is not positive
+    definite gets the 1-based row at which that was found in info[i] and NaN from that row on; no other block is affected.
+    Returns info.  Asynchronous on the current stream; nothing is read back."""
+    return _cholupdate(R, V, info, -1)
+
+
 class VarBatch:
     """A batch of SPD blocks of DIFFERENT sizes 0 <= n_i <= 256 inside ONE flat fp64 device tensor: block i is the n_i x n_i column-major block
     at element offsets[i] with leading dimension ld[i].  sizes, ld, offsets: host sequences of ints; ld=None: ld[i] = max(n_i, 1);
@@ -207,6 +264,39 @@ class VarBatch:
         call writes.  Returns R.  Asynchronous on the current stream."""
         lapack.engine._potri_vbatched(self._plan, self._flat(R, "R"), self.batch, _info(info, R), _PACK_VI, fill=bool(symmetric))
         return R
+
+    def _cholupdate(self, R, V, info, sign):
+        self._flat(R, "R")
+        _check(V, "V", (1, 2))
+        V2 = V.unsqueeze(0) if V.dim() == 1 else V
+        if V2.shape[1] != self.rows:
+            raise _lib.CapitalError("V must be (rows,) or (k, rows) with rows = %d, got shape %s" % (self.rows, tuple(V.shape)))
+        k = V2.shape[0]
+        if self.rows > 1 and V2.stride(1) != 1:
+            raise _lib.CapitalError("every column of V must be contiguous, got strides %s" % (V.stride(),))
+        ldv = V2.stride(0) if k > 1 else max(self.rows, 1)
+        if ldv < self.rows:
+            raise _lib.CapitalError("V: columns overlap (strides %s)" % (V.stride(),))
+        if V.device != R.device:
+            raise _lib.CapitalError("R and V live on different devices")
+        info = _own_info(info, self.batch, R)
+        lapack.engine._cholupdate_vbatched(self._plan, R, V2, k, ldv, self.batch, sign, info if self.batch > 0 else None, _PACK_VU)
+        return info
+
+    def update(self, R, V, info=None):
+        """Rank-k update of the factors potrf left in R, in place: block i <- the factor of A_i + V_i V_i^T.  V: fp64 device tensor of shape
+        (rows,) or (k, rows) with stride(-1) == 1 - every column of the stacked V, block i owning entries row_offsets[i] .. row_offsets[i] + n_i
+        of it; V is not written.  In torch's row-major reading (.block) the LOWER triangle holds L and afterwards L' with L' L'^T = A_i + V_i V_i^T.
+        info: int32 device tensor of batch entries in batch order, read and written in place - a block with info != 0 is not touched, the
+        entries of empty blocks are neither read nor written - or None for a fresh zeroed one.  Returns info.  Every block gets the bits of
+        the fixed-size update on it alone.  Asynchronous on the current stream."""
+        return self._cholupdate(R, V, info, 1)
+
+    def downdate(self, R, V, info=None):
+        """Rank-k downdate, in place: block i <- the factor of A_i - V_i V_i^T; arguments as in update.  In torch's row-major reading (.block)
+        the LOWER triangle afterwards holds L' with L' L'^T = A_i - V_i V_i^T.  A block whose matrix is not positive definite gets the 1-based
+        row at which that was found in info[i] and NaN from that row on.  Returns info.  Asynchronous on the current stream."""
+        return self._cholupdate(R, V, info, -1)
 
     def block(self, A, i):
         """The n_i x n_i view of block i of the flat tensor A in torch's row-major reading: block(A, i)[r, c] is element (c, r) of the

@@ -25,14 +25,13 @@
 #include <algorithm>
 #include <mutex>
 
+#include "chud_step.h"   // dotk and the two row steps (UK_MAX, UH): shared with cholupdate_batched.hip
 #include "common.h"
 
 namespace {
 
 constexpr int UT = 64;                // tile width = lanes of the one wavefront of a workgroup
 constexpr int ULD = UT + 1;           // LDS leading dimension of the tile (odd: row-wise and column-wise reads hit distinct banks)
-constexpr int UK_MAX = 16;            // columns of V per pass
-constexpr int UH = UK_MAX + 4;        // doubles per row of a reflector block: w_r[0 .. 16), a, b, g, one unused
 constexpr int CHUD_POLLS = 1 << 21;   // ~ 1 us per poll: a workgroup gives up after seconds (an item it waits for takes microseconds)
 constexpr int CHUD_HDR = 4;           // counter words in front of pub / parts
 
@@ -78,19 +77,6 @@ __device__ __forceinline__ void publish(int* w, int v) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (threadIdx.x == 0) ist(w, v);
-}
-
-// sum_q x[q] y[q] in a fixed order: four interleaved partial sums (one for NK < 4), added pairwise
-template <int NK>
-__device__ __forceinline__ double dotk(const double* x, const double (&y)[NK]) {
-  constexpr int P = NK >= 4 ? 4 : 1;
-  double s[P];
-#pragma unroll
-  for (int p = 0; p < P; p++) s[p] = x[p] * y[p];
-#pragma unroll
-  for (int q = P; q < NK; q++) s[q % P] = fma(x[q], y[q], s[q % P]);
-  if constexpr (P == 4) return (s[0] + s[1]) + (s[2] + s[3]);
-  else return s[0];
 }
 
 // One work item.  j: block row, i: block column (i == j: the diagonal item D_j).  wait = false in the recovery launch and in the
@@ -154,40 +140,16 @@ __device__ __forceinline__ bool chud_item(const ChudArgs& a, int j, int i, bool 
   if (diag) {
     for (int r = 0; r < rv; r++) {
       if (c == r) {
-        const double rr = col[r];
-        const double rho2 = fma(a.sigma, dotk<NK>(w, w), rr * rr);
-        double rho = sqrt(rho2);
-        if (!(rho2 > 0.0) || !(rho2 <= 1.79769313486231570815e308)) {
-          if (a.info) atomicCAS(a.info, 0, (int)r0 + r + 1);
-          rho = __builtin_nan("");
-        }
-        double* hr = Hs + r * UH;
-#pragma unroll
-        for (int q = 0; q < NK; q++) hr[q] = w[q];
-        hr[UK_MAX] = rr / rho; hr[UK_MAX + 1] = a.sigma / rho; hr[UK_MAX + 2] = 1.0 / (rr + rho);   // w_r = 0: a = 1 exactly, the row keeps its bits
+        bool fail;
+        const double rho = chud_reflector<NK>(w, col[r], a.sigma, Hs + r * UH, fail);
+        if (fail && a.info) atomicCAS(a.info, 0, (int)r0 + r + 1);
         col[r] = rho;
       }
       __syncthreads();
-      if (c > r) {
-        const double* hr = Hs + r * UH;
-        const double x = col[r];
-        const double y = fma(hr[UK_MAX], x, hr[UK_MAX + 1] * dotk<NK>(hr, w));
-        const double s = (x + y) * hr[UK_MAX + 2];
-#pragma unroll
-        for (int q = 0; q < NK; q++) w[q] = fma(-hr[q], s, w[q]);
-        col[r] = y;
-      }
+      if (c > r) col[r] = chud_apply<NK>(Hs + r * UH, col[r], w);
     }
   } else {
-    for (int r = 0; r < UT; r++) {
-      const double* hr = Hs + r * UH;
-      const double x = col[r];
-      const double y = fma(hr[UK_MAX], x, hr[UK_MAX + 1] * dotk<NK>(hr, w));
-      const double s = (x + y) * hr[UK_MAX + 2];
-#pragma unroll
-      for (int q = 0; q < NK; q++) w[q] = fma(-hr[q], s, w[q]);
-      col[r] = y;
-    }
+    for (int r = 0; r < UT; r++) col[r] = chud_apply<NK>(Hs + r * UH, col[r], w);
   }
   __syncthreads();
 

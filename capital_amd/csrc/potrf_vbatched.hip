@@ -32,16 +32,11 @@
 #include "batched_blocked.h"
 #include "batched_inverse.h"
 #include "capital_amd.h"
+#include "vbatch_plan.h"   // VbRec, cap_vbatch_plan, vb_per_group: shared with cholupdate_batched.hip
 
 namespace {
 
-constexpr int VB_CLASSES = 7;          // NP = 8, 16, 32, 64, then NBLK = 2, 3, 4
 constexpr int VB_MAX = 256;
-
-struct VbRec {                         // one block, in batch order
-  int64_t off, ld, row;                // offset of the block, its leading dimension, its first row of the stacked right-hand sides
-  int64_t n;
-};
 
 struct VbArgs {                        // one class of one call
   const VbRec* rec;
@@ -305,7 +300,6 @@ __global__ __launch_bounds__(64 * pi_waves(NBLK)) void potri_vbatched_blocked_ke
 
 int64_t vb_clip(__int128 v) { return v > (__int128)INT64_MAX ? INT64_MAX : (int64_t)v; }
 int vb_class(int64_t n) { return n <= 8 ? 0 : n <= 16 ? 1 : n <= 32 ? 2 : n <= 64 ? 3 : n <= 128 ? 4 : n <= 192 ? 5 : 6; }
-int vb_per_group(int cls) { return cls == 0 ? 8 : cls == 1 ? 4 : cls == 2 ? 2 : 1; }      // blocks per workgroup
 
 enum { VB_FACTOR, VB_SOLVE, VB_INVERSE };
 
@@ -341,17 +335,6 @@ void vb_launch(int op, int cls, unsigned grid, hipStream_t s, const VbArgs& g) {
 }
 
 }  // namespace
-
-struct cap_vbatch_plan {
-  int64_t batch = 0, total = 0, rows = 0, nmax = 0;
-  int nonempty = 0;
-  std::vector<VbRec> rec;                      // host copies: the access notes and cap_vbatch_plan_table read them
-  std::vector<int64_t> list[VB_CLASSES];
-  int device = -1;                             // -1: made in a process without a device - a description only, no entry runs on it
-  VbRec* d_rec = nullptr;
-  int64_t* d_list = nullptr;                   // the class lists back to back
-  int64_t list_at[VB_CLASSES] = {0, 0, 0, 0, 0, 0, 0};
-};
 
 namespace {
 

@@ -4,7 +4,8 @@ _potrs (A X = B with the factor of _potrf), _potri (A^-1 from that factor), _cho
 pivoted factorization of a semidefinite A, LAPACK's dpstrf), _lansy (the 1-norm of a symmetric matrix), _pocon (the reciprocal condition
 number from the factor, LAPACK's dpocon), _poerr (the error bounds of LAPACK's dporfs) and _potrf_batched / _potrs_batched / _trtri_batched /
 _potri_batched (the factor, solve, triangular inverse and SPD inverse of many small blocks of one size in one launch) and _potrf_vbatched /
-_potrs_vbatched / _potri_vbatched (the same for blocks of different sizes, described by a cap_vbatch_plan) have no counterpart upstream.
+_potrs_vbatched / _potri_vbatched (the same for blocks of different sizes, described by a cap_vbatch_plan) and _cholupdate_batched /
+_cholupdate_vbatched (the rank-k update / downdate of those factors) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -51,6 +52,8 @@ class Method(enum.IntEnum):
     AlapackPotriVbatched = 0xF  # extension: not in the reference's enum
     AlapackGeqrf = 0x10
     AlapackOrgqr = 0x11
+    AlapackCholupdateBatched = 0x12    # extension: not in the reference's enum
+    AlapackCholupdateVbatched = 0x13   # extension: not in the reference's enum
 
 
 class ArgPack_potrf:
@@ -140,6 +143,18 @@ class ArgPack_potrs_vbatched:
 class ArgPack_potri_vbatched:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPotriVbatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_cholupdate_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackCholupdateBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_cholupdate_vbatched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackCholupdateVbatched
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -375,6 +390,34 @@ class engine:
         st = L.cap_dpotri_vbatched(plan, int(srcPackage.uplo), dptr(matrixR), engine._batched_info(info, batch), 1 if fill else 0,
                                    cur_stream(stream))
         _lib.check(st, "lapack::engine::_potri_vbatched")
+
+    @staticmethod
+    def _cholupdate_batched(matrixR, matrixV, n, k, ldr, stride_r, ldv, stride_v, batch, sign, info, srcPackage, stream=None):
+        """The upper factors R_i (n x n, n <= 256, column-major, ld ldr, at matrixR + i stride_r; what _potrf_batched left) <- the factors of
+        R_i^T R_i + sign V_i V_i^T, V_i n x k (ld ldv, at matrixV + i stride_v, not written), sign = +1 / -1, in one launch
+        (cap_dcholupdate_batched).  info: a contiguous int32 device tensor of batch entries, read AND written - a block with info != 0 on
+        entry is not touched, a downdate that finds its matrix not positive definite leaves the 1-based row there - or None: every block is
+        swept and nothing is reported.  Every block gets the bits of _cholupdate on it alone.  Asynchronous; nothing is read back."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        _batched_blocked(None, n)
+        L = _lib.lib()
+        st = L.cap_dcholupdate_batched(int(srcPackage.uplo), int(sign), n, k, dptr(matrixR), ldr, stride_r, dptr(matrixV), ldv, stride_v, batch,
+                                       engine._batched_info(info, batch), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_cholupdate_batched")
+
+    @staticmethod
+    def _cholupdate_vbatched(plan, matrixR, matrixV, k, ldv, batch, sign, info, srcPackage, stream=None):
+        """The factors _potrf_vbatched left in matrixR (n_i <= 256) <- those of R_i^T R_i + sign V_i V_i^T with the stacked matrixV
+        ((sum n_i) x k, column-major, ld ldv; block i owns the rows behind the prefix sum of n): cap_dcholupdate_vbatched, one launch per
+        non-empty size class.  info as in _cholupdate_batched, batch order; the entries of empty blocks are neither read nor written.
+        Asynchronous; nothing is read back."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        L = _lib.lib()
+        st = L.cap_dcholupdate_vbatched(plan, int(srcPackage.uplo), int(sign), k, dptr(matrixR), dptr(matrixV), ldv,
+                                        engine._batched_info(info, batch), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_cholupdate_vbatched")
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

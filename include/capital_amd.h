@@ -272,6 +272,41 @@ int cap_dpotrs_vbatched(const cap_vbatch_plan* p, int uplo, int64_t nrhs, const 
                         void* stream);
 int cap_dpotri_vbatched(const cap_vbatch_plan* p, int uplo, double* R, const int* info, int fill, void* stream);
 
+/* Batched rank-k update / downdate of the factors (csrc/cholupdate_batched.hip; the vendor libraries have no such call): block i is the
+ * n x n column-major block at R + i * stride_r (leading dimension ldr), 1 <= n <= 256, holding the upper factor
+ * cap_dpotrf_batched[_blocked] left; on return it holds the upper factor of R_i^T R_i + sign V_i V_i^T, in place.  V_i is n x k
+ * column-major at V + i * stride_v (leading dimension ldv) and is never written.  sign = +1 or -1, one value per call.  Any k >= 0: k > 16
+ * is taken as consecutive passes of at most 16 columns inside the same launch, each a complete update, as in cap_dcholupdate.
+ * info (batch device ints, may be NULL) is INPUT AND OUTPUT, the convention of cap_cholinv_update on a plan: a block with info[i] != 0 on
+ * entry is not touched and its info[i] stays; otherwise info[i] stays 0 or becomes the 1-based row at which A_i - V_i V_i^T was found
+ * not positive definite - the sweep carries on with NaN, as in the single-matrix call, and no other block is affected.  NULL: every block
+ * is swept.  A block has one owner (a wavefront's lane group for n <= 64, a workgroup of four waves above) and its rows go in order: the
+ * first failing row is written with a plain store.
+ * The contract is that of the batched entries above: ONE launch per call on a 1-D grid, no `work` argument, no allocation, no memset, no
+ * atomics, no mutex, no helper stream, no host synchronisation; asynchronous on `stream`, callable from several host threads; 64-bit
+ * offsets.  Never read: the strictly lower triangle of R, rows n .. ld - 1 of every column of R and V, the gaps between blocks, everything
+ * behind the last block.  Never written: the same, and all of V.
+ * THE BIT CONTRACT: for every block with info[i] == 0 on entry, R_i and info[i] come out bit for bit as cap_dcholupdate (either driver)
+ * writes them for that block alone with the same sign, k and data - whatever batch, its index, ldr, ldv, the strides, the alignment and
+ * whichever blocks share its wavefront.  (Both run the row steps of csrc/chud_step.h: rho^2 = fma(sigma, w.w, r_rr^2), a correctly rounded
+ * square root and three divisions per row, the dot products in four interleaved partial sums over NK = 1 / 2 / 4 / 8 / 16 >= the pass's
+ * columns, zero padded.)
+ * Argument rules, in this order, all decided before any device call: sign other than +1 / -1, n < 0, k < 0, batch < 0 -> CAP_ERR_ARG; with
+ * n k batch > 0: NULL R or V, ldr < n, ldv < n, and with batch > 1 stride_r < ldr n or stride_v < ldv k -> CAP_ERR_ARG; uplo = LOWER ->
+ * CAP_ERR_UNSUPPORTED; n > 256 -> CAP_ERR_UNSUPPORTED; 64 < n with a batch beyond one grid dimension -> CAP_ERR_UNSUPPORTED; n == 0,
+ * k == 0 or batch == 0 -> CAP_OK without a launch, nothing touched.
+ * cap_dcholupdate_vbatched: the same on a cap_vbatch_plan (sizes 0 <= n_i <= 256, per-block offset / ld for R).  V is the STACKED matrix,
+ * (sum n_i) x k column-major with ldv >= sum n_i; block i owns rows row_off[i] .. row_off[i] + n_i, exactly as B in cap_dpotrs_vbatched.
+ * One launch per non-empty size class (seven at most); every block gets, bit for bit, what cap_dcholupdate_batched gives for it with
+ * batch = 1.  info has `batch` entries in batch order; entries of empty blocks are neither read nor written.  Entry rules, in this order:
+ * NULL plan, bad sign, k < 0, NULL R / V when something would be launched, ldv < sum n_i -> CAP_ERR_ARG; uplo = LOWER ->
+ * CAP_ERR_UNSUPPORTED; an empty or all-zero-size plan or k = 0 -> CAP_OK without a launch; a plan made without a device -> CAP_ERR_HIP
+ * unless nothing would be launched.                                                                                                       */
+int cap_dcholupdate_batched(int uplo, int sign, int64_t n, int64_t k, double* R, int64_t ldr, int64_t stride_r, const double* V, int64_t ldv,
+                            int64_t stride_v, int64_t batch, int* info, void* stream);
+int cap_dcholupdate_vbatched(const cap_vbatch_plan* p, int uplo, int sign, int64_t k, double* R, const double* V, int64_t ldv, int* info,
+                             void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
