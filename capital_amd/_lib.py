@@ -46,6 +46,10 @@ SIGNATURES = {
     "cap_dpotri_vbatched": (cint, [ptr, cint, ptr, ptr, cint, ptr]),
     "cap_dcholupdate_batched": (cint, [cint, cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
     "cap_dcholupdate_vbatched": (cint, [ptr, cint, cint, i64, ptr, ptr, i64, ptr, ptr]),
+    "cap_dtrsm_batched": (cint, [cint, cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr, i64, ptr]),
+    "cap_dtrmm_batched": (cint, [cint, cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
+    "cap_dtrsm_vbatched": (cint, [ptr, cint, cint, i64, ptr, ptr, i64, ptr, ptr, i64, ptr]),
+    "cap_dtrmm_vbatched": (cint, [ptr, cint, cint, i64, ptr, ptr, i64, ptr, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

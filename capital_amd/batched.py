@@ -9,6 +9,8 @@ Blocks of DIFFERENT sizes: VarBatch, a plan built once from host-side sizes (cap
 potri take one launch per size class that occurs.
 update / downdate (and VarBatch.update / .downdate): the factors of A_i +- V_i V_i^T from those of A_i in place, one launch
 (cap_dcholupdate_batched / cap_dcholupdate_vbatched, csrc/cholupdate_batched.hip).
+trsm / trmm / mahalanobis (and the VarBatch forms): ONE half of the factor applied to B - R^-T B, R^-1 B, R^T B, R B - and the squared
+Mahalanobis distances, one launch (cap_dtrsm_batched / cap_dtrmm_batched / cap_dtrsm_vbatched / cap_dtrmm_vbatched, csrc/trsm_batched.hip).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
@@ -25,6 +27,10 @@ _PACK_VS = lapack.ArgPack_potrs_vbatched(lapack.Order.AlapackColumnMajor, lapack
 _PACK_VI = lapack.ArgPack_potri_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_U = lapack.ArgPack_cholupdate_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_VU = lapack.ArgPack_cholupdate_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_TS = lapack.ArgPack_trsm_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_TM = lapack.ArgPack_trmm_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VTS = lapack.ArgPack_trsm_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VTM = lapack.ArgPack_trmm_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 
 
 def _check(t, name, dims):
@@ -172,6 +178,61 @@ def downdate(R, V, info=None):
     return _cholupdate(R, V, info, -1)
 
 
+def _rhs(R, B):
+    """(batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b) of potrs's operands, checked as potrs checks them"""
+    batch, n, ldr, stride_r = _blocks(R, "R")
+    _check(B, "B", (2, 3))
+    B3 = B.unsqueeze(1) if B.dim() == 2 else B
+    if B3.shape[0] != batch or B3.shape[2] != n:
+        raise _lib.CapitalError("B must be (batch, nrhs, n) or (batch, n) with batch = %d, n = %d, got shape %s" % (batch, n, tuple(B.shape)))
+    nrhs = B3.shape[1]
+    if n > 1 and B3.stride(2) != 1:
+        raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
+    ldb = B3.stride(1) if nrhs > 1 else max(n, 1)
+    stride_b = B3.stride(0)
+    if ldb < n or (batch > 1 and stride_b < ldb * nrhs):
+        raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
+    if B.device != R.device:
+        raise _lib.CapitalError("R and B live on different devices")
+    return batch, n, ldr, stride_r, B3, nrhs, ldb, max(stride_b, 0)
+
+
+def trsm(R, B, trans=True, info=None, sumsq=False):
+    """ONE of the two substitutions of potrs, in place: B[i] <- R_i^-T B[i] (trans=True) or R_i^-1 B[i] (trans=False) with the upper
+    factors potrf left in R (same layout rules as potrf's A, n <= 256; B as in potrs: (batch, nrhs, n) or (batch, n), stride(-1) == 1).
+    In torch's row-major reading of the same memory the LOWER triangle of R[i] holds L = R^T = torch.linalg.cholesky(A)[i]:
+    trsm(trans=True) is L^-1 b (whitening: the result has identity covariance when b ~ N(0, A_i)), trsm(trans=False) is L^-T b.
+    trsm(trans=True) followed by trsm(trans=False) leaves the bits of potrs.  A zero on the diagonal is not detected.
+    info: what potrf returned, or None - a block with info != 0 gets NaN.  sumsq=True: also returns q, a fresh fp64 tensor of shape
+    (batch, nrhs) - (batch,) for a 2-D B - with the sums of squares of the result's columns, computed in the same launch by a fixed
+    recurrence (q = fma(x_r, x_r, q) in ascending r).  Returns B, or (B, q).  Asynchronous on the current stream."""
+    batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b = _rhs(R, B)
+    q = torch.zeros((batch, nrhs), dtype=torch.float64, device=R.device) if sumsq else None
+    lapack.engine._trsm_batched(R, B3, n, nrhs, ldr, stride_r, ldb, stride_b, batch, bool(trans), _info(info, R), _PACK_TS,
+                                sumsq=q if batch * nrhs > 0 else None, ldq=nrhs)
+    if not sumsq:
+        return B
+    return B, (q[:, 0] if B.dim() == 2 else q)
+
+
+def trmm(R, B, trans=True, info=None):
+    """The product with one half of the factor, in place: B[i] <- R_i^T B[i] (trans=True) or R_i B[i] (trans=False); R, B and info as in
+    trsm.  In torch's row-major reading the LOWER triangle of R[i] holds L = R^T: trmm(trans=True) is L z (sampling: L z ~ N(0, A_i) for
+    z ~ N(0, I)), trmm(trans=False) is L^T z.  It undoes trsm with the same trans up to rounding.  Returns B.  Asynchronous on the
+    current stream."""
+    batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b = _rhs(R, B)
+    lapack.engine._trmm_batched(R, B3, n, nrhs, ldr, stride_r, ldb, stride_b, batch, bool(trans), _info(info, R), _PACK_TM)
+    return B
+
+
+def mahalanobis(R, B, info=None):
+    """Squared Mahalanobis distances d^2 = b^T A_i^-1 b of the columns of B[i] from the factors potrf left in R: trsm(R, B, trans=True,
+    sumsq=True).  B is left WHITENED (L^-1 b with L = R^T, what torch reads in the LOWER triangle of R[i]).  Returns q of shape
+    (batch, nrhs), or (batch,) for a 2-D B; NaN for a block with info != 0.  With potrf's logdet the Gaussian log-density is
+    -(d^2 + logdet + n log 2 pi) / 2.  Asynchronous on the current stream."""
+    return trsm(R, B, trans=True, info=info, sumsq=True)[1]
+
+
 class VarBatch:
     """A batch of SPD blocks of DIFFERENT sizes 0 <= n_i <= 256 inside ONE flat fp64 device tensor: block i is the n_i x n_i column-major block
     at element offsets[i] with leading dimension ld[i].  sizes, ld, offsets: host sequences of ints; ld=None: ld[i] = max(n_i, 1);
@@ -297,6 +358,52 @@ class VarBatch:
         the LOWER triangle afterwards holds L' with L' L'^T = A_i - V_i V_i^T.  A block whose matrix is not positive definite gets the 1-based
         row at which that was found in info[i] and NaN from that row on.  Returns info.  Asynchronous on the current stream."""
         return self._cholupdate(R, V, info, -1)
+
+    def _stacked(self, R, B):
+        """(B2, nrhs, ldb) of potrs's stacked right-hand sides, checked as potrs checks them"""
+        self._flat(R, "R")
+        _check(B, "B", (1, 2))
+        B2 = B.unsqueeze(0) if B.dim() == 1 else B
+        if B2.shape[1] != self.rows:
+            raise _lib.CapitalError("B must be (rows,) or (nrhs, rows) with rows = %d, got shape %s" % (self.rows, tuple(B.shape)))
+        nrhs = B2.shape[0]
+        if self.rows > 1 and B2.stride(1) != 1:
+            raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
+        ldb = B2.stride(0) if nrhs > 1 else max(self.rows, 1)
+        if ldb < self.rows:
+            raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
+        if B.device != R.device:
+            raise _lib.CapitalError("R and B live on different devices")
+        return B2, nrhs, ldb
+
+    def trsm(self, R, B, trans=True, info=None, sumsq=False):
+        """ONE of the two substitutions of potrs on every block, in place: block i of the stacked B (as in potrs: (rows,) or (nrhs, rows))
+        <- R_i^-T b (trans=True) or R_i^-1 b (trans=False).  In torch's row-major reading (.block) the LOWER triangle holds L = R^T:
+        trans=True is L^-1 b (whitening), trans=False is L^-T b.  info: what potrf returned, or None - a block with info != 0 gets NaN.
+        sumsq=True: also returns q, a fresh fp64 tensor of shape (batch, nrhs) - (batch,) for a 1-D B - in batch order with the sums of
+        squares of every block's result columns (0 for an empty block).  Every block gets the bits of the fixed-size trsm on it alone.
+        Returns B, or (B, q).  Asynchronous on the current stream."""
+        B2, nrhs, ldb = self._stacked(R, B)
+        q = torch.zeros((self.batch, nrhs), dtype=torch.float64, device=R.device) if sumsq else None
+        lapack.engine._trsm_vbatched(self._plan, R, B2, nrhs, ldb, self.batch, bool(trans), _info(info, R), _PACK_VTS,
+                                     sumsq=q if self.batch * nrhs > 0 else None, ldq=nrhs)
+        if not sumsq:
+            return B
+        return B, (q[:, 0] if B.dim() == 1 else q)
+
+    def trmm(self, R, B, trans=True, info=None):
+        """The product with one half of every block's factor, in place: block i of the stacked B <- R_i^T b (trans=True) or R_i b
+        (trans=False).  In torch's row-major reading (.block) the LOWER triangle holds L = R^T: trans=True is L z (sampling), trans=False
+        is L^T z.  Returns B.  Asynchronous on the current stream."""
+        B2, nrhs, ldb = self._stacked(R, B)
+        lapack.engine._trmm_vbatched(self._plan, R, B2, nrhs, ldb, self.batch, bool(trans), _info(info, R), _PACK_VTM)
+        return B
+
+    def mahalanobis(self, R, B, info=None):
+        """Squared Mahalanobis distances b_i^T A_i^-1 b_i of every block's piece of the stacked B: trsm(R, B, trans=True, sumsq=True).
+        B is left WHITENED (L^-1 b with L = R^T, what torch reads in the LOWER triangle of .block).  Returns q of shape (batch, nrhs), or
+        (batch,) for a 1-D B, in batch order; 0 for an empty block, NaN for a block with info != 0.  Asynchronous on the current stream."""
+        return self.trsm(R, B, trans=True, info=info, sumsq=True)[1]
 
     def block(self, A, i):
         """The n_i x n_i view of block i of the flat tensor A in torch's row-major reading: block(A, i)[r, c] is element (c, r) of the

@@ -5,7 +5,8 @@ pivoted factorization of a semidefinite A, LAPACK's dpstrf), _lansy (the 1-norm 
 number from the factor, LAPACK's dpocon), _poerr (the error bounds of LAPACK's dporfs) and _potrf_batched / _potrs_batched / _trtri_batched /
 _potri_batched (the factor, solve, triangular inverse and SPD inverse of many small blocks of one size in one launch) and _potrf_vbatched /
 _potrs_vbatched / _potri_vbatched (the same for blocks of different sizes, described by a cap_vbatch_plan) and _cholupdate_batched /
-_cholupdate_vbatched (the rank-k update / downdate of those factors) have no counterpart upstream.
+_cholupdate_vbatched (the rank-k update / downdate of those factors) and _trsm_batched / _trmm_batched / _trsm_vbatched / _trmm_vbatched
+(one triangular solve or product with those factors) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -54,6 +55,10 @@ class Method(enum.IntEnum):
     AlapackOrgqr = 0x11
     AlapackCholupdateBatched = 0x12    # extension: not in the reference's enum
     AlapackCholupdateVbatched = 0x13   # extension: not in the reference's enum
+    AlapackTrsmBatched = 0x14          # extension: not in the reference's enum
+    AlapackTrmmBatched = 0x15          # extension: not in the reference's enum
+    AlapackTrsmVbatched = 0x16         # extension: not in the reference's enum
+    AlapackTrmmVbatched = 0x17         # extension: not in the reference's enum
 
 
 class ArgPack_potrf:
@@ -156,6 +161,30 @@ class ArgPack_cholupdate_vbatched:
     def __init__(self, order, uplo):
         self.method = Method.AlapackCholupdateVbatched
         self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_trsm_batched:
+    def __init__(self, order, uplo, diag=Diag.AlapackNonUnit):
+        self.method = Method.AlapackTrsmBatched
+        self.order, self.uplo, self.diag = Order(order), UpLo(uplo), Diag(diag)
+
+
+class ArgPack_trmm_batched:
+    def __init__(self, order, uplo, diag=Diag.AlapackNonUnit):
+        self.method = Method.AlapackTrmmBatched
+        self.order, self.uplo, self.diag = Order(order), UpLo(uplo), Diag(diag)
+
+
+class ArgPack_trsm_vbatched:
+    def __init__(self, order, uplo, diag=Diag.AlapackNonUnit):
+        self.method = Method.AlapackTrsmVbatched
+        self.order, self.uplo, self.diag = Order(order), UpLo(uplo), Diag(diag)
+
+
+class ArgPack_trmm_vbatched:
+    def __init__(self, order, uplo, diag=Diag.AlapackNonUnit):
+        self.method = Method.AlapackTrmmVbatched
+        self.order, self.uplo, self.diag = Order(order), UpLo(uplo), Diag(diag)
 
 
 BATCHED_SMALL_MAX = 64      # cap_dpotrf_batched / cap_dpotrs_batched: a wavefront per block
@@ -418,6 +447,68 @@ class engine:
         st = L.cap_dcholupdate_vbatched(plan, int(srcPackage.uplo), int(sign), k, dptr(matrixR), dptr(matrixV), ldv,
                                         engine._batched_info(info, batch), cur_stream(stream))
         _lib.check(st, "lapack::engine::_cholupdate_vbatched")
+
+    @staticmethod
+    def _tri_pack(srcPackage):
+        if srcPackage.order != Order.AlapackColumnMajor or getattr(srcPackage, "diag", Diag.AlapackNonUnit) != Diag.AlapackNonUnit:
+            raise _lib.CapitalError("only AlapackColumnMajor / AlapackNonUnit is supported")
+
+    @staticmethod
+    def _sumsq_ptr(sumsq, batch, nrhs, ldq):
+        if sumsq is None:
+            return None
+        if (not isinstance(sumsq, torch.Tensor) or not sumsq.is_cuda or sumsq.dtype != torch.float64 or not sumsq.is_contiguous()
+                or ldq < nrhs or sumsq.numel() < batch * ldq):
+            raise _lib.CapitalError("sumsq must be a contiguous fp64 device tensor of batch x ldq entries with ldq >= nrhs")
+        return sumsq.data_ptr()
+
+    @staticmethod
+    def _trsm_batched(matrixR, matrixB, n, nrhs, ldr, stride_r, ldb, stride_b, batch, trans, info, srcPackage, sumsq=None, ldq=0, stream=None):
+        """B_i (n x nrhs, ld ldb, at matrixB + i stride_b) <- R_i^-T B_i (trans) or R_i^-1 B_i (not trans) with the upper triangles R_i at
+        matrixR + i stride_r (ld ldr; what _potrf_batched left), n <= 256, in one launch (cap_dtrsm_batched).  info: what _potrf_batched
+        returned, or None; a block with info != 0 gets NaN.  sumsq: None, or a contiguous fp64 device tensor of batch x ldq entries
+        (ldq >= nrhs) that receives the sums of squares of the result's columns, computed in the same launch.  Asynchronous."""
+        engine._tri_pack(srcPackage)
+        _batched_blocked(None, n)
+        q = engine._sumsq_ptr(sumsq, batch, nrhs, ldq)
+        L = _lib.lib()
+        st = L.cap_dtrsm_batched(int(srcPackage.uplo), 1 if trans else 0, n, nrhs, dptr(matrixR), ldr, stride_r, dptr(matrixB), ldb, stride_b,
+                                 batch, engine._batched_info(info, batch), q, ldq, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_trsm_batched")
+
+    @staticmethod
+    def _trmm_batched(matrixR, matrixB, n, nrhs, ldr, stride_r, ldb, stride_b, batch, trans, info, srcPackage, stream=None):
+        """B_i <- R_i^T B_i (trans) or R_i B_i (not trans); arguments and layout as in _trsm_batched, n <= 256, one launch
+        (cap_dtrmm_batched).  A block with info != 0 gets NaN.  Asynchronous."""
+        engine._tri_pack(srcPackage)
+        _batched_blocked(None, n)
+        L = _lib.lib()
+        st = L.cap_dtrmm_batched(int(srcPackage.uplo), 1 if trans else 0, n, nrhs, dptr(matrixR), ldr, stride_r, dptr(matrixB), ldb, stride_b,
+                                 batch, engine._batched_info(info, batch), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_trmm_batched")
+
+    @staticmethod
+    def _trsm_vbatched(plan, matrixR, matrixB, nrhs, ldb, batch, trans, info, srcPackage, sumsq=None, ldq=0, stream=None):
+        """The stacked right-hand sides matrixB ((sum n_i) x nrhs, ld ldb) <- R_i^-T B_i (trans) or R_i^-1 B_i block by block with the
+        factors _potrf_vbatched left in matrixR (n_i <= 256; a plan refuses larger blocks when it is made): cap_dtrsm_vbatched, one launch
+        per non-empty size class.  info, sumsq (batch x ldq, batch order; rows of empty blocks are not written) as in _trsm_batched.
+        Asynchronous."""
+        engine._tri_pack(srcPackage)
+        q = engine._sumsq_ptr(sumsq, batch, nrhs, ldq)
+        L = _lib.lib()
+        st = L.cap_dtrsm_vbatched(plan, int(srcPackage.uplo), 1 if trans else 0, nrhs, dptr(matrixR), dptr(matrixB), ldb,
+                                  engine._batched_info(info, batch), q, ldq, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_trsm_vbatched")
+
+    @staticmethod
+    def _trmm_vbatched(plan, matrixR, matrixB, nrhs, ldb, batch, trans, info, srcPackage, stream=None):
+        """The stacked matrixB <- R_i^T B_i (trans) or R_i B_i block by block (n_i <= 256; a plan refuses larger blocks when it is made):
+        cap_dtrmm_vbatched, one launch per non-empty size class.  Asynchronous."""
+        engine._tri_pack(srcPackage)
+        L = _lib.lib()
+        st = L.cap_dtrmm_vbatched(plan, int(srcPackage.uplo), 1 if trans else 0, nrhs, dptr(matrixR), dptr(matrixB), ldb,
+                                  engine._batched_info(info, batch), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_trmm_vbatched")
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

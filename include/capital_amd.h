@@ -307,6 +307,52 @@ int cap_dcholupdate_batched(int uplo, int sign, int64_t n, int64_t k, double* R,
 int cap_dcholupdate_vbatched(const cap_vbatch_plan* p, int uplo, int sign, int64_t k, double* R, const double* V, int64_t ldv, int* info,
                              void* stream);
 
+/* Batched triangular solves and products on the factors (csrc/trsm_batched.hip): one HALF of what cap_dpotrs_batched[_blocked] applies, and
+ * the products that go with it.  Left side, upper triangle, non-unit diagonal, no alpha, fp64, one GPU, 1 <= n <= 256.  R, ldr, stride_r, B,
+ * ldb, stride_b, batch and info are exactly those of cap_dpotrs_batched[_blocked]: block i is the n x n column-major block at
+ * R + i * stride_r holding an upper triangle (what cap_dpotrf_batched[_blocked] left, or any other), B_i is n x nrhs at B + i * stride_b.
+ *   cap_dtrsm_batched  trans = CAP_TRANS: B_i <- R_i^-T B_i (the whitened right-hand sides: with L = R^T, y = L^-1 b);
+ *                      trans = CAP_NOTRANS: B_i <- R_i^-1 B_i.
+ *   cap_dtrmm_batched  trans = CAP_TRANS: B_i <- R_i^T B_i (colouring: x = L z draws from N(0, A_i));  trans = CAP_NOTRANS: B_i <- R_i B_i.
+ * Any nrhs >= 0: more right-hand sides than a pass holds (NP = 8, 16, 32 or 64 >= n for n <= 64, 16 above) are further passes inside the
+ * launch.  The strictly lower triangle of R, rows n .. ld - 1 of every column of R and B, the gaps between blocks and columns and everything
+ * behind the last block are never addressed.  A zero on the diagonal is not detected, as in cap_dtrtri_batched: it shows as IEEE infinities
+ * and NaNs inside its own block.  info (may be NULL): a block with info[i] != 0 gets NaN in its B_i - and in its sumsq row - and its R is
+ * not interpreted.
+ * sumsq (cap_dtrsm_* only, may be NULL; ldq >= nrhs): sumsq[i * ldq + k] = the sum of the squares of column k of the RESULT of block i -
+ * with trans = CAP_TRANS the squared Mahalanobis distance b^T A_i^-1 b.  It is computed inside the same launch from the values that are
+ * stored to B, by the one thread that owns the column, as   q = 0;  for r = 0 .. n - 1: q = fma(x_r, x_r, q)   - the same recurrence on
+ * the wavefront path (n <= 64) and on the workgroup path: the value is a function of the stored column alone.
+ * The contract is that of the batched entries above: ONE launch per call on a 1-D grid (n <= 64: a wavefront per 64 / NP blocks; above: a
+ * workgroup of four waves per block), no `work` argument, no allocation, no memset, no atomics, no mutex, no helper stream, no host
+ * synchronisation, nothing between workgroups; asynchronous on `stream`, callable from several host threads; 64-bit offsets; correctly
+ * rounded divisions.  The order of the additions of a product's row sum is fixed (it is written at the head of csrc/trsm_batched.hip): for
+ * n <= 64 from the diagonal outwards, one fused multiply-add per term.
+ * THE BIT CONTRACTS.
+ *   1. HALVES = WHOLE: cap_dtrsm_batched(CAP_TRANS) followed by cap_dtrsm_batched(CAP_NOTRANS) on the same B leaves, bit for bit, what
+ *      cap_dpotrs_batched_blocked leaves, for every n, layout, nrhs and batch - the NaN of failed blocks included.
+ *   2. PLAN = FIXED: every block of a plan call gets the bits of the fixed-size entry on it alone with batch = 1, sumsq included,
+ *      whichever blocks share its wavefront or its class.
+ *   3. COLUMN INDEPENDENCE: a column's result and its sumsq do not depend on how many columns travel with it or on its position among them.
+ * Argument rules, in this order, all decided before any device call: trans other than CAP_NOTRANS / CAP_TRANS, n < 0, nrhs < 0, batch < 0; a
+ * NULL R or B with n nrhs batch > 0; ldr < n or ldb < n; with batch > 1: stride_r < ldr n or stride_b < ldb nrhs; sumsq given with ldq <
+ * nrhs -> CAP_ERR_ARG; then uplo = LOWER -> CAP_ERR_UNSUPPORTED; then n > 256 -> CAP_ERR_UNSUPPORTED; then a grid beyond one dimension
+ * (2^31 - 1 workgroups) -> CAP_ERR_UNSUPPORTED; then n == 0, nrhs == 0 or batch == 0 -> CAP_OK without a launch.
+ * cap_dtrsm_vbatched / cap_dtrmm_vbatched: the same on a cap_vbatch_plan, with the layout of cap_dpotrs_vbatched - B is the STACKED
+ * (sum n_i) x nrhs matrix with ldb >= sum n_i, block i owning rows row_off[i] .. row_off[i] + n_i.  One launch per non-empty size class
+ * (seven at most).  info and sumsq are indexed by the BATCH index i; the words of empty blocks are neither read nor written.  Entry rules,
+ * in this order: NULL plan, bad trans, nrhs < 0, a NULL R / B when something would be launched, ldb < sum n_i, sumsq given with ldq < nrhs
+ * -> CAP_ERR_ARG; uplo = LOWER -> CAP_ERR_UNSUPPORTED; an empty or all-zero-size plan or nrhs = 0 -> CAP_OK without a launch; a plan made
+ * without a device -> CAP_ERR_HIP unless nothing would be launched.                                                                       */
+int cap_dtrsm_batched(int uplo, int trans, int64_t n, int64_t nrhs, const double* R, int64_t ldr, int64_t stride_r, double* B, int64_t ldb,
+                      int64_t stride_b, int64_t batch, const int* info, double* sumsq, int64_t ldq, void* stream);
+int cap_dtrmm_batched(int uplo, int trans, int64_t n, int64_t nrhs, const double* R, int64_t ldr, int64_t stride_r, double* B, int64_t ldb,
+                      int64_t stride_b, int64_t batch, const int* info, void* stream);
+int cap_dtrsm_vbatched(const cap_vbatch_plan* p, int uplo, int trans, int64_t nrhs, const double* R, double* B, int64_t ldb, const int* info,
+                       double* sumsq, int64_t ldq, void* stream);
+int cap_dtrmm_vbatched(const cap_vbatch_plan* p, int uplo, int trans, int64_t nrhs, const double* R, double* B, int64_t ldb, const int* info,
+                       void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
