@@ -50,6 +50,8 @@ SIGNATURES = {
     "cap_dtrmm_batched": (cint, [cint, cint, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr]),
     "cap_dtrsm_vbatched": (cint, [ptr, cint, cint, i64, ptr, ptr, i64, ptr, ptr, i64, ptr]),
     "cap_dtrmm_vbatched": (cint, [ptr, cint, cint, i64, ptr, ptr, i64, ptr, ptr]),
+    "cap_dsyrk_batched": (cint, [cint, cint, i64, i64, dbl, ptr, i64, i64, dbl, ptr, i64, i64, ptr, cint, i64, ptr]),
+    "cap_dsyrk_vbatched": (cint, [ptr, cint, cint, i64, dbl, ptr, i64, dbl, ptr, ptr, cint, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

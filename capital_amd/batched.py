@@ -11,12 +11,14 @@ update / downdate (and VarBatch.update / .downdate): the factors of A_i +- V_i V
 (cap_dcholupdate_batched / cap_dcholupdate_vbatched, csrc/cholupdate_batched.hip).
 trsm / trmm / mahalanobis (and the VarBatch forms): ONE half of the factor applied to B - R^-T B, R^-1 B, R^T B, R B - and the squared
 Mahalanobis distances, one launch (cap_dtrsm_batched / cap_dtrmm_batched / cap_dtrsm_vbatched / cap_dtrmm_vbatched, csrc/trsm_batched.hip).
+syrk / schur (and VarBatch.syrk): FORMING the blocks - alpha V^T V + beta C (+ shift I) into the triangle potrf reads, and the Schur
+complement C - B A^-1 B^T from a factor, one launch per product (cap_dsyrk_batched / cap_dsyrk_vbatched, csrc/syrk_batched.hip).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
 import torch
 
-from . import _lib, lapack
+from . import _lib, blas, lapack
 
 _PACK_F = lapack.ArgPack_potrf_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_S = lapack.ArgPack_potrs_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
@@ -233,6 +235,88 @@ def mahalanobis(R, B, info=None):
     return trsm(R, B, trans=True, info=info, sumsq=True)[1]
 
 
+def _span(t):
+    """[first, last) byte addresses a tensor's elements lie in"""
+    if t.numel() == 0:
+        return 0, 0
+    return t.data_ptr(), t.data_ptr() + 8 * (sum((d - 1) * abs(st) for d, st in zip(t.shape, t.stride())) + 1)
+
+
+def _no_overlap(V, C):
+    (a0, a1), (b0, b1) = _span(V), _span(C)
+    if a0 < b1 and b0 < a1:
+        raise _lib.CapitalError("V and C overlap")
+
+
+def _syrk_pack(trans, alpha, beta):
+    return blas.ArgPack_syrk(blas.Order.AblasColumnMajor, blas.UpLo.AblasUpper, blas.Transpose.AblasTrans if trans else blas.Transpose.AblasNoTrans,
+                             alpha, beta)
+
+
+def _shift(shift, batch, ref):
+    """None, a number or a (batch,) fp64 device tensor -> None or the tensor"""
+    if shift is None:
+        return None
+    if isinstance(shift, (int, float)):
+        return torch.full((max(batch, 1),), float(shift), dtype=torch.float64, device=ref.device)
+    _check(shift, "shift", (1,))
+    if shift.shape[0] != batch or not shift.is_contiguous():
+        raise _lib.CapitalError("shift must be a number or a contiguous (batch,) tensor with batch = %d, got shape %s" % (batch, tuple(shift.shape)))
+    if shift.device != ref.device:
+        raise _lib.CapitalError("shift lives on another device")
+    return shift
+
+
+def syrk(V, C=None, trans=False, alpha=1.0, beta=0.0, shift=None, symmetric=False):
+    """Forms the blocks potrf factors, one launch: C[i] <- alpha V[i]^T V[i] + beta C[i] (+ shift[i] I) in torch's reading.
+    trans=False: V is (batch, k, n) or (batch, n) with stride(-1) == 1, exactly update's V - C[i] is the Gram matrix of the k rows V[i, q]
+    (their sum of outer products: normal equations, covariances).  trans=True: V is (batch, n, k) with stride(-1) == 1 and
+    C[i] <- alpha V[i] V[i]^T + beta C[i] (linear-kernel matrices; the layout of potrs's and trsm's B).  Any k; n <= 256.  V is not written
+    and must not overlap C.
+    C: fp64 device tensor of shape (batch, n, n) under potrf's layout rules, or None (only with beta == 0) for a fresh zero-initialised one.
+    The triangle that is written is the one potrf reads - the upper triangle of the column-major block, which is the LOWER triangle of C[i]
+    in torch's row-major reading - so potrf(syrk(X)) works without a copy; what torch reads as the strictly upper triangle is neither read
+    nor written, unless symmetric=True (the C ABI's fill = 1): then it becomes the bit-identical mirror.  beta == 0 does not read C (NaN there
+    does not propagate).  shift: None, a number, or a (batch,) fp64 device tensor added to the diagonals (ridge terms).
+    The summation order is fixed (csrc/syrk_batched.hip): every element is a function of its two rows of V alone, the same bits for any batch,
+    layout or trans.  Returns C.  Asynchronous on the current stream."""
+    _check(V, "V", (2, 3))
+    V3 = V.unsqueeze(2 if trans else 1) if V.dim() == 2 else V
+    batch = V3.shape[0]
+    n, k = (V3.shape[1], V3.shape[2]) if trans else (V3.shape[2], V3.shape[1])
+    inner, outer = (k, n) if trans else (n, k)               # V3 is (batch, outer, inner): `outer` contiguous runs of `inner` elements
+    if inner > 1 and V3.stride(2) != 1:
+        raise _lib.CapitalError("V must have stride(-1) == 1, got strides %s" % (V.stride(),))
+    ldv = V3.stride(1) if outer > 1 else max(inner, 1)
+    stride_v = V3.stride(0)
+    if ldv < inner or (batch > 1 and stride_v < ldv * outer):
+        raise _lib.CapitalError("V: columns overlap (strides %s)" % (V.stride(),))
+    if C is None:
+        if beta != 0:
+            raise _lib.CapitalError("C=None needs beta == 0")
+        C = torch.zeros((batch, n, n), dtype=torch.float64, device=V.device)
+    cb, cn, ldc, stride_c = _blocks(C, "C")
+    if cb != batch or cn != n:
+        raise _lib.CapitalError("C must be (batch, n, n) with batch = %d, n = %d, got shape %s" % (batch, n, tuple(C.shape)))
+    if C.device != V.device:
+        raise _lib.CapitalError("V and C live on different devices")
+    _no_overlap(V, C)
+    blas.engine._syrk_batched(V3, C, n, k, ldv, max(stride_v, 0), ldc, stride_c, batch, _syrk_pack(trans, alpha, beta),
+                              shift=_shift(shift, batch, V), fill=bool(symmetric))
+    return C
+
+
+def schur(R, B, C, info=None):
+    """Schur complements (conditional covariances) from the factors potrf left in R, in place: C[i] <- C[i] - B[i] A_i^-1 B[i]^T for B of shape
+    (batch, m, n) and C of shape (batch, m, m), m <= 256, n <= 256 - two launches: trsm(R, B, trans=True, info=info), then
+    syrk(B, C, trans=True, alpha=-1, beta=1).  B is left WHITENED: row j of B[i] holds L^-1 b_j with L = R^T (what torch reads in the LOWER
+    triangle of R[i]).  The triangle of C that is read and written is the one potrf reads (the LOWER triangle in torch's reading).  A block
+    with info != 0 gets NaN in its B from trsm and through it NaN in that triangle of its C.  Returns C.  Asynchronous on the current
+    stream."""
+    trsm(R, B, trans=True, info=info)
+    return syrk(B, C, trans=True, alpha=-1.0, beta=1.0)
+
+
 class VarBatch:
     """A batch of SPD blocks of DIFFERENT sizes 0 <= n_i <= 256 inside ONE flat fp64 device tensor: block i is the n_i x n_i column-major block
     at element offsets[i] with leading dimension ld[i].  sizes, ld, offsets: host sequences of ints; ld=None: ld[i] = max(n_i, 1);
@@ -404,6 +488,42 @@ class VarBatch:
         B is left WHITENED (L^-1 b with L = R^T, what torch reads in the LOWER triangle of .block).  Returns q of shape (batch, nrhs), or
         (batch,) for a 1-D B, in batch order; 0 for an empty block, NaN for a block with info != 0.  Asynchronous on the current stream."""
         return self.trsm(R, B, trans=True, info=info, sumsq=True)[1]
+
+    def syrk(self, V, C=None, trans=False, alpha=1.0, beta=0.0, shift=None, symmetric=False):
+        """Forms every block from its piece of the stacked V, one launch per size class: block i <- alpha V_i^T V_i + beta C_i (+ shift[i] I)
+        in torch's reading (.block).  trans=False: V is (k, rows) or (rows,) with stride(-1) == 1, update's stacked V - block i owns entries
+        row_offsets[i] .. row_offsets[i] + n_i of every row.  trans=True: V is (rows, k) with stride(-1) == 1, block i owning rows
+        row_offsets[i] .. row_offsets[i] + n_i, and block i <- alpha V_i V_i^T + beta C_i.  C: the flat tensor of at least .total
+        elements, or None (only with beta == 0) for a fresh zeroed one.  The triangle potrf reads is written (the LOWER one in torch's
+        reading); symmetric=True mirrors it bit for bit.  shift: None, a number or a (batch,) fp64 device tensor in batch order.  Padding,
+        gaps and empty blocks are neither read nor written.  Every block gets the bits of the fixed-size syrk on it alone.  Returns C.
+        Asynchronous on the current stream."""
+        _check(V, "V", (1, 2))
+        if trans and V.dim() != 2:
+            raise _lib.CapitalError("V must be (rows, k) with trans=True, got shape %s" % (tuple(V.shape),))
+        V2 = V.unsqueeze(0) if V.dim() == 1 else V
+        rows, k = (V2.shape[0], V2.shape[1]) if trans else (V2.shape[1], V2.shape[0])
+        if rows != self.rows:
+            raise _lib.CapitalError("V must be %s with rows = %d, got shape %s" % ("(rows, k)" if trans else "(rows,) or (k, rows)", self.rows, tuple(V.shape)))
+        inner, outer = (k, rows) if trans else (rows, k)
+        if inner > 1 and V2.stride(1) != 1:
+            raise _lib.CapitalError("V must have stride(-1) == 1, got strides %s" % (V.stride(),))
+        ldv = V2.stride(0) if outer > 1 else max(inner, 1)
+        if ldv < inner:
+            raise _lib.CapitalError("V: columns overlap (strides %s)" % (V.stride(),))
+        if C is None:
+            if beta != 0:
+                raise _lib.CapitalError("C=None needs beta == 0")
+            if self.device is None:
+                raise _lib.CapitalError("there is no device - there is no CPU path")
+            C = torch.zeros(max(self.total, 1), dtype=torch.float64, device=torch.device("cuda", self.device))[:self.total]
+        self._flat(C, "C")
+        if V.device != C.device:
+            raise _lib.CapitalError("V and C live on different devices")
+        _no_overlap(V, C)
+        blas.engine._syrk_vbatched(self._plan, V2, C, k, ldv, self.batch, _syrk_pack(trans, alpha, beta), shift=_shift(shift, self.batch, C),
+                                   fill=bool(symmetric))
+        return C
 
     def block(self, A, i):
         """The n_i x n_i view of block i of the flat tensor A in torch's row-major reading: block(A, i)[r, c] is element (c, r) of the

@@ -5,6 +5,8 @@ buffers (torch tensors or raw device addresses) and run the hand-written MFMA ke
 libcapital_amd.so.  No CPU path: missing library or non-device pointers fail loudly."""
 import enum
 
+import torch
+
 from . import _lib
 from ._util import dptr, cur_stream, scratch
 
@@ -92,6 +94,40 @@ class engine:
         st = _lib.lib().cap_dsyrk(int(srcPackage.uplo), int(srcPackage.transposeA), n, k, srcPackage.alpha, dptr(matrixA), lda,
                                   srcPackage.beta, dptr(matrixC), ldc, cur_stream(stream))
         _lib.check(st, "blas::engine::_syrk")
+
+    @staticmethod
+    def _shift_ptr(shift, batch):
+        if shift is None:
+            return None
+        if (not isinstance(shift, torch.Tensor) or not shift.is_cuda or shift.dtype != torch.float64 or not shift.is_contiguous()
+                or shift.numel() < batch):
+            raise _lib.CapitalError("shift must be a contiguous fp64 device tensor of batch entries")
+        return shift.data_ptr()
+
+    @staticmethod
+    def _syrk_batched(matrixV, matrixC, n, k, ldv, stride_v, ldc, stride_c, batch, srcPackage, shift=None, fill=False, stream=None):
+        """The upper triangle of every column-major n x n block C_i (matrixC + i stride_c, ld ldc) <- beta C_i + alpha op(V_i) op(V_i)^T
+        (+ shift[i] I), n <= 256, any k, in one launch (cap_dsyrk_batched).  AblasNoTrans: V_i is n x k (ld ldv >= n) at matrixV + i stride_v;
+        AblasTrans: V_i is k x n (ld ldv >= k) and C = alpha V^T V + beta C.  alpha, beta, uplo and transposeA come from the ArgPack_syrk.
+        shift: None, or a contiguous fp64 device tensor of batch entries; fill: the strictly lower triangle becomes the bit-identical
+        mirror.  beta == 0 does not read C.  Asynchronous."""
+        _require_colmajor(srcPackage.order)
+        if n > 256:
+            raise _lib.CapitalError("_syrk_batched takes blocks of at most 256 rows, got n = %d" % n)
+        st = _lib.lib().cap_dsyrk_batched(int(srcPackage.uplo), int(srcPackage.transposeA), n, k, srcPackage.alpha, dptr(matrixV), ldv, stride_v,
+                                          srcPackage.beta, dptr(matrixC), ldc, stride_c, engine._shift_ptr(shift, batch), 1 if fill else 0, batch,
+                                          cur_stream(stream))
+        _lib.check(st, "blas::engine::_syrk_batched")
+
+    @staticmethod
+    def _syrk_vbatched(plan, matrixV, matrixC, k, ldv, batch, srcPackage, shift=None, fill=False, stream=None):
+        """The same for the blocks of a cap_vbatch_plan (n_i <= 256; a plan refuses larger blocks when it is made): matrixC is the flat tensor
+        of the plan, matrixV the stacked (sum n_i) x k matrix (AblasNoTrans, ldv >= sum n_i) or the k x (sum n_i) one (AblasTrans,
+        ldv >= k); shift in batch order.  cap_dsyrk_vbatched, one launch per non-empty size class.  Asynchronous."""
+        _require_colmajor(srcPackage.order)
+        st = _lib.lib().cap_dsyrk_vbatched(plan, int(srcPackage.uplo), int(srcPackage.transposeA), k, srcPackage.alpha, dptr(matrixV), ldv,
+                                           srcPackage.beta, dptr(matrixC), engine._shift_ptr(shift, batch), 1 if fill else 0, cur_stream(stream))
+        _lib.check(st, "blas::engine::_syrk_vbatched")
 
     @staticmethod
     def _trsm(matrixA, matrixB, m, n, lda, ldb, srcPackage, stream=None):

@@ -26,7 +26,8 @@ NO_SCRATCH = ("dgemm_tn_dma_kernel", "gram256_kernel", "qrapply256_kernel", "bf1
               "potrf_vbatched_kernel", "potrs_vbatched_kernel", "potri_vbatched_kernel", "potrf_vbatched_blocked_kernel", "potrs_vbatched_blocked_kernel",
               "potri_vbatched_blocked_kernel", "chud_batched_kernel", "chud_vbatched_kernel", "chud_batched_blocked_kernel",
               "chud_vbatched_blocked_kernel", "tri_batched_kernel", "tri_vbatched_kernel", "tri_batched_blocked_kernel",
-              "tri_vbatched_blocked_kernel")
+              "tri_vbatched_blocked_kernel", "syrk_batched_kernel", "syrk_vbatched_kernel", "syrk_batched_blocked_kernel",
+              "syrk_vbatched_blocked_kernel")
 
 
 def sources():

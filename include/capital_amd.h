@@ -353,6 +353,50 @@ int cap_dtrsm_vbatched(const cap_vbatch_plan* p, int uplo, int trans, int64_t nr
 int cap_dtrmm_vbatched(const cap_vbatch_plan* p, int uplo, int trans, int64_t nrhs, const double* R, double* B, int64_t ldb, const int* info,
                        void* stream);
 
+/* Batched symmetric rank-k products INTO the layout the batched factor reads (csrc/syrk_batched.hip): the step before cap_dpotrf_batched.
+ * For every block the upper triangle of the column-major n x n block C_i (at C + i * stride_c, leading dimension ldc) becomes
+ *   beta C_i + alpha op(V_i) op(V_i)^T (+ shift[i] I),   0 <= n <= 256, any k >= 0 (the loop over k is inside the one launch), fp64, one GPU.
+ *   trans = CAP_NOTRANS: V_i is n x k column-major at V + i * stride_v with ldv >= n - exactly the V of cap_dcholupdate_batched.
+ *   trans = CAP_TRANS:   V_i is k x n column-major with ldv >= k and C = alpha V^T V + beta C - the B / W layout of cap_dpotrs_batched and
+ *                        cap_dtrsm_batched, contraction over the rows: with W = R^-T B from cap_dtrsm_batched, alpha = -1, beta = 1 gives the
+ *                        Schur complement C - B^T A^-1 B.
+ * V is never written and must not overlap C.  shift: NULL, or `batch` device doubles; shift[i] is added to every diagonal element after
+ * the alpha / beta combination, with one rounding (ridge and Levenberg-Marquardt terms).  fill: that of cap_dpotri_batched - 1 makes the
+ * strictly lower triangle the bit-identical mirror, copied and never computed a second time; the lower triangle is never read.
+ * The arithmetic, the same on both paths: s_rc = sum_q v_rq v_cq on the fp64 16 x 16 x 4 MFMA from a zero accumulator with K ascending,
+ * four columns per instruction (rows >= n and columns >= k enter as +0.0 and are never addressed); t = alpha * s;
+ * out = (beta == 0) ? t : fma(beta, c_old, t); on the diagonal, out = out + shift[i].  beta == 0: C is not read, NaN or Inf there do not
+ * propagate.  alpha == 0 or k == 0: V is not addressed and C_i <- beta C_i (+ shift[i] I).
+ * The contract is that of the batched entries above: ONE launch per call on a 1-D grid (n <= 64: a wavefront per 64 / NP blocks; above: a
+ * workgroup of four waves per block), no `work` argument, no allocation, no memset, no atomics, no mutex, no helper stream, no host
+ * synchronisation, nothing between workgroups; asynchronous on `stream`; 64-bit offsets.  The strictly lower triangle of C with fill = 0,
+ * rows n .. ld - 1 of every column of C and V, the gaps between blocks and everything behind the last block are never addressed.  A large k
+ * with few blocks leaves most of the chip idle: k is not split across workgroups (that would need atomics or scratch).
+ * THE BIT CONTRACTS.
+ *   1. PLAN = FIXED: every block of a plan call gets the bits of the fixed-size entry on it alone with batch = 1, whichever blocks share
+ *      its wavefront or its class.
+ *   2. LAYOUT INDEPENDENCE: a block's bits are a function of (n, k, alpha, beta, shift[i], its data) only - not of batch, index, ldc, ldv,
+ *      the strides or the alignment.
+ *   3. TRANS IS A LAYOUT: the same mathematical V handed over in either layout gives the same bits.
+ *   4. ELEMENT INDEPENDENCE: c_rc is a function of rows r and c of V (and k, alpha, beta, c_old, shift[i]) alone: it equals element (0, 1) of
+ *      the 2 x 2 block formed from those two rows, for r = c element (0, 0) of the 1 x 1 block - one recurrence on both paths.
+ * Argument rules, in this order, all decided before any device call: trans other than CAP_NOTRANS / CAP_TRANS, n < 0, k < 0, batch < 0, fill
+ * other than 0 / 1; a NULL C with n batch > 0; a NULL V with n k batch > 0 and alpha != 0; ldc < n; ldv < n (CAP_NOTRANS) or ldv < k
+ * (CAP_TRANS); with batch > 1: stride_c < ldc n, stride_v < ldv k (CAP_NOTRANS) or ldv n (CAP_TRANS) -> CAP_ERR_ARG; then uplo = LOWER ->
+ * CAP_ERR_UNSUPPORTED; then n > 256 -> CAP_ERR_UNSUPPORTED; then a grid beyond one dimension (2^31 - 1 workgroups) -> CAP_ERR_UNSUPPORTED;
+ * then n == 0 or batch == 0 -> CAP_OK without a launch.
+ * cap_dsyrk_vbatched: the same on a cap_vbatch_plan.  C is the flat tensor with the plan's offsets and leading dimensions.  CAP_NOTRANS: V
+ * is the STACKED (sum n_i) x k matrix with ldv >= sum n_i, as in cap_dcholupdate_vbatched; CAP_TRANS: V is k x (sum n_i) with ldv >= k,
+ * block i owning columns row_off[i] .. row_off[i] + n_i.  shift is indexed by the BATCH index i.  One launch per non-empty size class
+ * (seven at most); the words of empty blocks are neither read nor written.  Entry rules, in this order: NULL plan, bad trans, k < 0, bad
+ * fill, a NULL C / V when something would be launched (V: with k > 0 and alpha != 0), ldv < sum n_i (CAP_NOTRANS) or ldv < k (CAP_TRANS)
+ * -> CAP_ERR_ARG; uplo = LOWER -> CAP_ERR_UNSUPPORTED; an empty or all-zero-size plan -> CAP_OK without a launch; a plan made without a
+ * device -> CAP_ERR_HIP unless nothing would be launched.                                                                                */
+int cap_dsyrk_batched(int uplo, int trans, int64_t n, int64_t k, double alpha, const double* V, int64_t ldv, int64_t stride_v, double beta,
+                      double* C, int64_t ldc, int64_t stride_c, const double* shift, int fill, int64_t batch, void* stream);
+int cap_dsyrk_vbatched(const cap_vbatch_plan* p, int uplo, int trans, int64_t k, double alpha, const double* V, int64_t ldv, double beta,
+                       double* C, const double* shift, int fill, void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
