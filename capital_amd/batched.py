@@ -58,6 +58,30 @@ def _blocks(A, name):
     return batch, n, lda, max(stride, 0)
 
 
+_COUNT = {"right-hand side": "nrhs", "column": "k"}     # what the docstrings call the number of columns of each kind
+
+
+def _columns(R, X, name, noun):
+    """(batch, n, ldr, stride_r, X3, count, ldx, stride_x) of the factors R and of X - potrs's and trsm's B (noun "right-hand side") or
+    update's V ("column"): (batch, count, n) or (batch, n), every column contiguous, no two overlapping, on R's device"""
+    batch, n, ldr, stride_r = _blocks(R, "R")
+    _check(X, name, (2, 3))
+    X3 = X.unsqueeze(1) if X.dim() == 2 else X
+    if X3.shape[0] != batch or X3.shape[2] != n:
+        raise _lib.CapitalError("%s must be (batch, %s, n) or (batch, n) with batch = %d, n = %d, got shape %s"
+                                % (name, _COUNT[noun], batch, n, tuple(X.shape)))
+    count = X3.shape[1]
+    if n > 1 and X3.stride(2) != 1:
+        raise _lib.CapitalError("every %s of %s must be contiguous, got strides %s" % (noun, name, X.stride()))
+    ldx = X3.stride(1) if count > 1 else max(n, 1)
+    stride_x = X3.stride(0)
+    if ldx < n or (batch > 1 and stride_x < ldx * count):
+        raise _lib.CapitalError("%s: %ss overlap (strides %s)" % (name, noun, X.stride()))
+    if X.device != R.device:
+        raise _lib.CapitalError("R and %s live on different devices" % name)
+    return batch, n, ldr, stride_r, X3, count, ldx, max(stride_x, 0)
+
+
 def potrf(A, logdet=False):
     """Cholesky factors of the batch, in place.  A: fp64 device tensor of shape (batch, n, n), n <= 256, with stride(2) == 1; stride(1) >= n and
     stride(0) >= n stride(1) are free.  Each A[i] is read as COLUMN-MAJOR memory with leading dimension stride(1) and its upper factor R
@@ -77,21 +101,8 @@ def potrs(R, B, info=None):
     upper triangle of R[i] is not referenced).  B: fp64 device tensor of shape (batch, nrhs, n) or (batch, n), every right-hand side
     contiguous (stride(-1) == 1); it is overwritten by the solutions.  info: what potrf returned, or None - a block with info != 0 gets NaN.
     Returns B.  Asynchronous on the current stream."""
-    batch, n, ldr, stride_r = _blocks(R, "R")
-    _check(B, "B", (2, 3))
-    B3 = B.unsqueeze(1) if B.dim() == 2 else B
-    if B3.shape[0] != batch or B3.shape[2] != n:
-        raise _lib.CapitalError("B must be (batch, nrhs, n) or (batch, n) with batch = %d, n = %d, got shape %s" % (batch, n, tuple(B.shape)))
-    nrhs = B3.shape[1]
-    if n > 1 and B3.stride(2) != 1:
-        raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
-    ldb = B3.stride(1) if nrhs > 1 else max(n, 1)
-    stride_b = B3.stride(0)
-    if ldb < n or (batch > 1 and stride_b < ldb * nrhs):
-        raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
-    if B.device != R.device:
-        raise _lib.CapitalError("R and B live on different devices")
-    lapack.engine._potrs_batched(R, B3, n, nrhs, ldr, stride_r, ldb, max(stride_b, 0), batch, info, _PACK_S)
+    batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b = _columns(R, B, "B", "right-hand side")
+    lapack.engine._potrs_batched(R, B3, n, nrhs, ldr, stride_r, ldb, stride_b, batch, info, _PACK_S)
     return B
 
 
@@ -140,22 +151,9 @@ def _own_info(info, batch, R):
 
 
 def _cholupdate(R, V, info, sign):
-    batch, n, ldr, stride_r = _blocks(R, "R")
-    _check(V, "V", (2, 3))
-    V3 = V.unsqueeze(1) if V.dim() == 2 else V
-    if V3.shape[0] != batch or V3.shape[2] != n:
-        raise _lib.CapitalError("V must be (batch, k, n) or (batch, n) with batch = %d, n = %d, got shape %s" % (batch, n, tuple(V.shape)))
-    k = V3.shape[1]
-    if n > 1 and V3.stride(2) != 1:
-        raise _lib.CapitalError("every column of V must be contiguous, got strides %s" % (V.stride(),))
-    ldv = V3.stride(1) if k > 1 else max(n, 1)
-    stride_v = V3.stride(0)
-    if ldv < n or (batch > 1 and stride_v < ldv * k):
-        raise _lib.CapitalError("V: columns overlap (strides %s)" % (V.stride(),))
-    if V.device != R.device:
-        raise _lib.CapitalError("R and V live on different devices")
+    batch, n, ldr, stride_r, V3, k, ldv, stride_v = _columns(R, V, "V", "column")
     info = _own_info(info, batch, R)
-    lapack.engine._cholupdate_batched(R, V3, n, k, ldr, stride_r, ldv, max(stride_v, 0), batch, sign, info if batch > 0 else None, _PACK_U)
+    lapack.engine._cholupdate_batched(R, V3, n, k, ldr, stride_r, ldv, stride_v, batch, sign, info if batch > 0 else None, _PACK_U)
     return info
 
 
@@ -180,25 +178,6 @@ def downdate(R, V, info=None):
     return _cholupdate(R, V, info, -1)
 
 
-def _rhs(R, B):
-    """(batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b) of potrs's operands, checked as potrs checks them"""
-    batch, n, ldr, stride_r = _blocks(R, "R")
-    _check(B, "B", (2, 3))
-    B3 = B.unsqueeze(1) if B.dim() == 2 else B
-    if B3.shape[0] != batch or B3.shape[2] != n:
-        raise _lib.CapitalError("B must be (batch, nrhs, n) or (batch, n) with batch = %d, n = %d, got shape %s" % (batch, n, tuple(B.shape)))
-    nrhs = B3.shape[1]
-    if n > 1 and B3.stride(2) != 1:
-        raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
-    ldb = B3.stride(1) if nrhs > 1 else max(n, 1)
-    stride_b = B3.stride(0)
-    if ldb < n or (batch > 1 and stride_b < ldb * nrhs):
-        raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
-    if B.device != R.device:
-        raise _lib.CapitalError("R and B live on different devices")
-    return batch, n, ldr, stride_r, B3, nrhs, ldb, max(stride_b, 0)
-
-
 def trsm(R, B, trans=True, info=None, sumsq=False):
     """ONE of the two substitutions of potrs, in place: B[i] <- R_i^-T B[i] (trans=True) or R_i^-1 B[i] (trans=False) with the upper
     factors potrf left in R (same layout rules as potrf's A, n <= 256; B as in potrs: (batch, nrhs, n) or (batch, n), stride(-1) == 1).
@@ -208,7 +187,7 @@ def trsm(R, B, trans=True, info=None, sumsq=False):
     info: what potrf returned, or None - a block with info != 0 gets NaN.  sumsq=True: also returns q, a fresh fp64 tensor of shape
     (batch, nrhs) - (batch,) for a 2-D B - with the sums of squares of the result's columns, computed in the same launch by a fixed
     recurrence (q = fma(x_r, x_r, q) in ascending r).  Returns B, or (B, q).  Asynchronous on the current stream."""
-    batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b = _rhs(R, B)
+    batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b = _columns(R, B, "B", "right-hand side")
     q = torch.zeros((batch, nrhs), dtype=torch.float64, device=R.device) if sumsq else None
     lapack.engine._trsm_batched(R, B3, n, nrhs, ldr, stride_r, ldb, stride_b, batch, bool(trans), _info(info, R), _PACK_TS,
                                 sumsq=q if batch * nrhs > 0 else None, ldq=nrhs)
@@ -222,7 +201,7 @@ def trmm(R, B, trans=True, info=None):
     trsm.  In torch's row-major reading the LOWER triangle of R[i] holds L = R^T: trmm(trans=True) is L z (sampling: L z ~ N(0, A_i) for
     z ~ N(0, I)), trmm(trans=False) is L^T z.  It undoes trsm with the same trans up to rounding.  Returns B.  Asynchronous on the
     current stream."""
-    batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b = _rhs(R, B)
+    batch, n, ldr, stride_r, B3, nrhs, ldb, stride_b = _columns(R, B, "B", "right-hand side")
     lapack.engine._trmm_batched(R, B3, n, nrhs, ldr, stride_r, ldb, stride_b, batch, bool(trans), _info(info, R), _PACK_TM)
     return B
 
@@ -386,19 +365,7 @@ class VarBatch:
         with stride(-1) == 1 - every right-hand side is the stacked vector, block i owning entries row_offsets[i] .. row_offsets[i] + n_i: the
         call applies the inverse of the block-diagonal matrix.  info: what potrf returned, or None - a block with info != 0 gets NaN.
         Returns B.  Asynchronous on the current stream."""
-        self._flat(R, "R")
-        _check(B, "B", (1, 2))
-        B2 = B.unsqueeze(0) if B.dim() == 1 else B
-        if B2.shape[1] != self.rows:
-            raise _lib.CapitalError("B must be (rows,) or (nrhs, rows) with rows = %d, got shape %s" % (self.rows, tuple(B.shape)))
-        nrhs = B2.shape[0]
-        if self.rows > 1 and B2.stride(1) != 1:
-            raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
-        ldb = B2.stride(0) if nrhs > 1 else max(self.rows, 1)
-        if ldb < self.rows:
-            raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
-        if B.device != R.device:
-            raise _lib.CapitalError("R and B live on different devices")
+        B2, nrhs, ldb = self._stacked(R, B, "B", "right-hand side")
         lapack.engine._potrs_vbatched(self._plan, R, B2, nrhs, ldb, self.batch, _info(info, R), _PACK_VS)
         return B
 
@@ -411,19 +378,7 @@ class VarBatch:
         return R
 
     def _cholupdate(self, R, V, info, sign):
-        self._flat(R, "R")
-        _check(V, "V", (1, 2))
-        V2 = V.unsqueeze(0) if V.dim() == 1 else V
-        if V2.shape[1] != self.rows:
-            raise _lib.CapitalError("V must be (rows,) or (k, rows) with rows = %d, got shape %s" % (self.rows, tuple(V.shape)))
-        k = V2.shape[0]
-        if self.rows > 1 and V2.stride(1) != 1:
-            raise _lib.CapitalError("every column of V must be contiguous, got strides %s" % (V.stride(),))
-        ldv = V2.stride(0) if k > 1 else max(self.rows, 1)
-        if ldv < self.rows:
-            raise _lib.CapitalError("V: columns overlap (strides %s)" % (V.stride(),))
-        if V.device != R.device:
-            raise _lib.CapitalError("R and V live on different devices")
+        V2, k, ldv = self._stacked(R, V, "V", "column")
         info = _own_info(info, self.batch, R)
         lapack.engine._cholupdate_vbatched(self._plan, R, V2, k, ldv, self.batch, sign, info if self.batch > 0 else None, _PACK_VU)
         return info
@@ -443,22 +398,23 @@ class VarBatch:
         row at which that was found in info[i] and NaN from that row on.  Returns info.  Asynchronous on the current stream."""
         return self._cholupdate(R, V, info, -1)
 
-    def _stacked(self, R, B):
-        """(B2, nrhs, ldb) of potrs's stacked right-hand sides, checked as potrs checks them"""
+    def _stacked(self, R, X, name, noun):
+        """(X2, count, ldx) of the flat factors R and of the stacked X - potrs's and trsm's B (noun "right-hand side") or update's V
+        ("column"): (rows,) or (count, rows), every column contiguous, no two overlapping, on R's device"""
         self._flat(R, "R")
-        _check(B, "B", (1, 2))
-        B2 = B.unsqueeze(0) if B.dim() == 1 else B
-        if B2.shape[1] != self.rows:
-            raise _lib.CapitalError("B must be (rows,) or (nrhs, rows) with rows = %d, got shape %s" % (self.rows, tuple(B.shape)))
-        nrhs = B2.shape[0]
-        if self.rows > 1 and B2.stride(1) != 1:
-            raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
-        ldb = B2.stride(0) if nrhs > 1 else max(self.rows, 1)
-        if ldb < self.rows:
-            raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
-        if B.device != R.device:
-            raise _lib.CapitalError("R and B live on different devices")
-        return B2, nrhs, ldb
+        _check(X, name, (1, 2))
+        X2 = X.unsqueeze(0) if X.dim() == 1 else X
+        if X2.shape[1] != self.rows:
+            raise _lib.CapitalError("%s must be (rows,) or (%s, rows) with rows = %d, got shape %s" % (name, _COUNT[noun], self.rows, tuple(X.shape)))
+        count = X2.shape[0]
+        if self.rows > 1 and X2.stride(1) != 1:
+            raise _lib.CapitalError("every %s of %s must be contiguous, got strides %s" % (noun, name, X.stride()))
+        ldx = X2.stride(0) if count > 1 else max(self.rows, 1)
+        if ldx < self.rows:
+            raise _lib.CapitalError("%s: %ss overlap (strides %s)" % (name, noun, X.stride()))
+        if X.device != R.device:
+            raise _lib.CapitalError("R and %s live on different devices" % name)
+        return X2, count, ldx
 
     def trsm(self, R, B, trans=True, info=None, sumsq=False):
         """ONE of the two substitutions of potrs on every block, in place: block i of the stacked B (as in potrs: (rows,) or (nrhs, rows))
@@ -467,7 +423,7 @@ class VarBatch:
         sumsq=True: also returns q, a fresh fp64 tensor of shape (batch, nrhs) - (batch,) for a 1-D B - in batch order with the sums of
         squares of every block's result columns (0 for an empty block).  Every block gets the bits of the fixed-size trsm on it alone.
         Returns B, or (B, q).  Asynchronous on the current stream."""
-        B2, nrhs, ldb = self._stacked(R, B)
+        B2, nrhs, ldb = self._stacked(R, B, "B", "right-hand side")
         q = torch.zeros((self.batch, nrhs), dtype=torch.float64, device=R.device) if sumsq else None
         lapack.engine._trsm_vbatched(self._plan, R, B2, nrhs, ldb, self.batch, bool(trans), _info(info, R), _PACK_VTS,
                                      sumsq=q if self.batch * nrhs > 0 else None, ldq=nrhs)
@@ -479,7 +435,7 @@ class VarBatch:
         """The product with one half of every block's factor, in place: block i of the stacked B <- R_i^T b (trans=True) or R_i b
         (trans=False).  In torch's row-major reading (.block) the LOWER triangle holds L = R^T: trans=True is L z (sampling), trans=False
         is L^T z.  Returns B.  Asynchronous on the current stream."""
-        B2, nrhs, ldb = self._stacked(R, B)
+        B2, nrhs, ldb = self._stacked(R, B, "B", "right-hand side")
         lapack.engine._trmm_vbatched(self._plan, R, B2, nrhs, ldb, self.batch, bool(trans), _info(info, R), _PACK_VTM)
         return B
 

@@ -1,6 +1,7 @@
 // The device side that potrf_batched_blocked.hip and potrf_vbatched.hip share: the factorization and the solve of ONE block of 65 .. 256
 // rows by one workgroup, as functions of the block's address, leading dimension and size.  The algorithm is described at the head of
 // potrf_batched_blocked.hip; the kernels there and in potrf_vbatched.hip differ in how a workgroup finds its block, and in nothing else.
+// The solve is bb_forward_sweep followed by bb_backward_sweep; trsm_batched.hip runs one of the two alone.
 #pragma once
 #include <math.h>
 
@@ -214,14 +215,95 @@ __device__ __forceinline__ void bb_factor_block(double* A, const int64_t lda, co
   }
 }
 
+// The two halves of the solve on the n x BB_KP slice s_y of right-hand sides (element (i, k) at i BB_LDY + k, rows n .. npad - 1 and dead
+// columns zero) by a workgroup of BB_THREADS; s_img: the diagonal block's image.  Each starts with a barrier and ends without one.
+__device__ __forceinline__ void bb_forward_sweep(const double* R, const int64_t ldr, const int n, double* s_img, double* s_y, const int lane, const int wave) {
+  const int lr = lane & 15, kg = lane >> 4;
+  const int nblk = (n + BB_NB - 1) / BB_NB;
+  // R^T y = b over the diagonal blocks in ascending order
+  for (int d = 0; d < nblk; d++) {
+    const int k0 = d * BB_NB, nb = n - k0 < BB_NB ? n - k0 : BB_NB, t0 = k0 + BB_NB;
+    __syncthreads();
+    bb_load_upper(R + k0 + (int64_t)k0 * ldr, ldr, nb, lane, wave, BB_WAVES, s_img);
+    __syncthreads();
+    if (wave == 0) {
+      double x[BB_NB];
+#pragma unroll
+      for (int i = 0; i < BB_NB; i++) x[i] = i < nb ? s_y[(k0 + i) * BB_LDY + lr] : 0.0;
+      bb_forward_steps(x, s_img + bb_opaque_zero(), nb, std::make_integer_sequence<int, BB_NB>{});
+#pragma unroll
+      for (int i = 0; i < BB_NB; i++)
+        if (i < nb && lane < BB_KP) s_y[(k0 + i) * BB_LDY + lr] = x[i];
+    }
+    __syncthreads();
+    // B2 -= R12^T Y1: MFMA A operand lane -> R[k0 + kk + kg][t0 + bi 16 + lr] (negated), B operand Y[k0 + kk + kg][lr]; D: row kg + 4 r, column lr
+    const int mt = t0 < n ? (n - t0 + 15) >> 4 : 0;
+    for (int bi = wave; bi < mt; bi += BB_WAVES) {
+      const int i0 = t0 + bi * 16;
+      const bool ain = i0 + lr < n;
+      const double* ra = R + (k0 + kg) + (int64_t)(i0 + lr) * ldr;
+      double* y = s_y + (i0 + kg) * BB_LDY + lr;
+      const double* yb = s_y + (k0 + kg) * BB_LDY + lr;
+      d4 acc;
+#pragma unroll
+      for (int r = 0; r < 4; r++) acc[r] = y[4 * r * BB_LDY];
+#pragma unroll
+      for (int kk = 0; kk < BB_NB; kk += 4) {
+        double a = 0.0;
+        if (ain) a = -ra[kk];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, yb[kk * BB_LDY], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        if (i0 + kg + 4 * r < n) y[4 * r * BB_LDY] = acc[r];      // rows at or beyond n stay zero
+    }
+  }
+}
+__device__ __forceinline__ void bb_backward_sweep(const double* R, const int64_t ldr, const int n, double* s_img, double* s_y, const int lane, const int wave) {
+  const int lr = lane & 15, kg = lane >> 4;
+  const int nblk = (n + BB_NB - 1) / BB_NB;
+  // R x = y over the diagonal blocks in descending order
+  for (int d = nblk - 1; d >= 0; d--) {
+    const int k0 = d * BB_NB, nb = n - k0 < BB_NB ? n - k0 : BB_NB;
+    __syncthreads();
+    bb_load_upper(R + k0 + (int64_t)k0 * ldr, ldr, nb, lane, wave, BB_WAVES, s_img);
+    __syncthreads();
+    if (wave == 0) {
+      double x[BB_NB];
+#pragma unroll
+      for (int i = 0; i < BB_NB; i++) x[i] = i < nb ? s_y[(k0 + i) * BB_LDY + lr] : 0.0;
+      bb_backward_steps(x, s_img + bb_opaque_zero(), nb, std::make_integer_sequence<int, BB_NB>{});
+#pragma unroll
+      for (int i = 0; i < BB_NB; i++)
+        if (i < nb && lane < BB_KP) s_y[(k0 + i) * BB_LDY + lr] = x[i];
+    }
+    __syncthreads();
+    // B1 -= R12 X2: MFMA A operand lane -> R[bi 16 + lr][k0 + kk + kg] (negated; zero at or beyond column n), B operand X[k0 + kk + kg][lr]
+    const int kend = (nb + 3) & ~3;
+    for (int bi = wave; bi < k0 / 16; bi += BB_WAVES) {
+      const double* ra = R + (bi * 16 + lr) + (int64_t)(k0 + kg) * ldr;
+      double* y = s_y + (bi * 16 + kg) * BB_LDY + lr;
+      const double* yb = s_y + (k0 + kg) * BB_LDY + lr;
+      d4 acc;
+#pragma unroll
+      for (int r = 0; r < 4; r++) acc[r] = y[4 * r * BB_LDY];
+      for (int kk = 0; kk < kend; kk += 4) {
+        double a = 0.0;
+        if (k0 + kk + kg < n) a = -ra[(int64_t)kk * ldr];
+        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, yb[kk * BB_LDY], acc, 0, 0, 0);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; r++) y[4 * r * BB_LDY] = acc[r];
+    }
+  }
+}
+
 // the solve of ONE block's right-hand sides by a workgroup of BB_THREADS; info (may be null): a block with info[slot] != 0 gets NaN
 __device__ __forceinline__ void bb_solve_block(const double* R, const int64_t ldr, double* B, const int64_t ldb, const int64_t nrhs, const int n, const int* info, const int64_t slot) {
   __shared__ double s_img[BbImg::SIZE];
   __shared__ double s_y[BB_MAX * BB_LDY];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int lr = lane & 15, kg = lane >> 4;
   const int npad = (n + 15) & ~15;
-  const int nblk = (n + BB_NB - 1) / BB_NB;
 
   if (info && info[slot] != 0) {     // a failed block: NaN (uniform over the workgroup)
     for (int64_t k = wave; k < nrhs; k += BB_WAVES)
@@ -234,79 +316,8 @@ __device__ __forceinline__ void bb_solve_block(const double* R, const int64_t ld
     for (int k = wave; k < BB_KP; k += BB_WAVES)
       for (int i = lane; i < npad; i += 64) s_y[i * BB_LDY + k] = (k < kc && i < n) ? B[i + (p0 + k) * ldb] : 0.0;
 
-    // R^T y = b over the diagonal blocks in ascending order
-    for (int d = 0; d < nblk; d++) {
-      const int k0 = d * BB_NB, nb = n - k0 < BB_NB ? n - k0 : BB_NB, t0 = k0 + BB_NB;
-      __syncthreads();
-      bb_load_upper(R + k0 + (int64_t)k0 * ldr, ldr, nb, lane, wave, BB_WAVES, s_img);
-      __syncthreads();
-      if (wave == 0) {
-        double x[BB_NB];
-#pragma unroll
-        for (int i = 0; i < BB_NB; i++) x[i] = i < nb ? s_y[(k0 + i) * BB_LDY + lr] : 0.0;
-        bb_forward_steps(x, s_img + bb_opaque_zero(), nb, std::make_integer_sequence<int, BB_NB>{});
-#pragma unroll
-        for (int i = 0; i < BB_NB; i++)
-          if (i < nb && lane < BB_KP) s_y[(k0 + i) * BB_LDY + lr] = x[i];
-      }
-      __syncthreads();
-      // B2 -= R12^T Y1: MFMA A operand lane -> R[k0 + kk + kg][t0 + bi 16 + lr] (negated), B operand Y[k0 + kk + kg][lr]; D: row kg + 4 r, column lr
-      const int mt = t0 < n ? (n - t0 + 15) >> 4 : 0;
-      for (int bi = wave; bi < mt; bi += BB_WAVES) {
-        const int i0 = t0 + bi * 16;
-        const bool ain = i0 + lr < n;
-        const double* ra = R + (k0 + kg) + (int64_t)(i0 + lr) * ldr;
-        double* y = s_y + (i0 + kg) * BB_LDY + lr;
-        const double* yb = s_y + (k0 + kg) * BB_LDY + lr;
-        d4 acc;
-#pragma unroll
-        for (int r = 0; r < 4; r++) acc[r] = y[4 * r * BB_LDY];
-#pragma unroll
-        for (int kk = 0; kk < BB_NB; kk += 4) {
-          double a = 0.0;
-          if (ain) a = -ra[kk];
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, yb[kk * BB_LDY], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++)
-          if (i0 + kg + 4 * r < n) y[4 * r * BB_LDY] = acc[r];      // rows at or beyond n stay zero
-      }
-    }
-
-    // R x = y over the diagonal blocks in descending order
-    for (int d = nblk - 1; d >= 0; d--) {
-      const int k0 = d * BB_NB, nb = n - k0 < BB_NB ? n - k0 : BB_NB;
-      __syncthreads();
-      bb_load_upper(R + k0 + (int64_t)k0 * ldr, ldr, nb, lane, wave, BB_WAVES, s_img);
-      __syncthreads();
-      if (wave == 0) {
-        double x[BB_NB];
-#pragma unroll
-        for (int i = 0; i < BB_NB; i++) x[i] = i < nb ? s_y[(k0 + i) * BB_LDY + lr] : 0.0;
-        bb_backward_steps(x, s_img + bb_opaque_zero(), nb, std::make_integer_sequence<int, BB_NB>{});
-#pragma unroll
-        for (int i = 0; i < BB_NB; i++)
-          if (i < nb && lane < BB_KP) s_y[(k0 + i) * BB_LDY + lr] = x[i];
-      }
-      __syncthreads();
-      // B1 -= R12 X2: MFMA A operand lane -> R[bi 16 + lr][k0 + kk + kg] (negated; zero at or beyond column n), B operand X[k0 + kk + kg][lr]
-      const int kend = (nb + 3) & ~3;
-      for (int bi = wave; bi < k0 / 16; bi += BB_WAVES) {
-        const double* ra = R + (bi * 16 + lr) + (int64_t)(k0 + kg) * ldr;
-        double* y = s_y + (bi * 16 + kg) * BB_LDY + lr;
-        const double* yb = s_y + (k0 + kg) * BB_LDY + lr;
-        d4 acc;
-#pragma unroll
-        for (int r = 0; r < 4; r++) acc[r] = y[4 * r * BB_LDY];
-        for (int kk = 0; kk < kend; kk += 4) {
-          double a = 0.0;
-          if (k0 + kk + kg < n) a = -ra[(int64_t)kk * ldr];
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, yb[kk * BB_LDY], acc, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) y[4 * r * BB_LDY] = acc[r];
-      }
-    }
+    bb_forward_sweep(R, ldr, n, s_img, s_y, lane, wave);
+    bb_backward_sweep(R, ldr, n, s_img, s_y, lane, wave);
     __syncthreads();
     for (int k = wave; k < kc; k += BB_WAVES)
       for (int i = lane; i < n; i += 64) B[i + (p0 + k) * ldb] = s_y[i * BB_LDY + k];

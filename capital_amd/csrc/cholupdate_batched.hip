@@ -1,6 +1,6 @@
 // Batched rank-k update / downdate of fp64 Cholesky factors (cap_dcholupdate_batched, cap_dcholupdate_vbatched): for every block
 // R_i'^T R_i' = R_i^T R_i + sigma V_i V_i^T in place on the upper factor, 1 <= n <= 256, V_i n x k (never written).  The batched member of
-// cholupdate.hip, in the shape of potrf_batched.hip / potrf_vbatched.hip: ONE launch per call (per non-empty size class on a plan) on a 1-D grid,
+// cholupdate.hip, in the shape of the batched factor: ONE launch per call (per non-empty size class on a plan) on a 1-D grid,
 // no scratch, no memset, no atomics, nothing between workgroups.
 //
 // THE ARITHMETIC is the row recurrence at the head of cholupdate.hip, through the functions of chud_step.h that file runs too: a block gets
@@ -24,11 +24,10 @@
 //
 // info (may be NULL) is input and output: a block with info != 0 on entry is not touched; otherwise the first failing row (1-based) is
 // written with a plain store - a block has one owner and its rows go in order - and the sweep carries on with NaN.
-// Variable sizes: the group's own n is the lane predicate while the wave loops to its largest n (potrf_vbatched.hip); no lane of a block
-// reads another block's data, so a block's bits do not depend on its neighbours.
-#include <algorithm>
-#include <type_traits>
-
+// Variable sizes: the group's own n is the lane predicate while the wave loops to its largest n (vb_wave_max of vbatch_plan.h, taken after
+// the info word); no lane of a block reads another block's data, so a block's bits do not depend on its neighbours.
+// SHARED (vbatch_plan.h): the argument rules, the grid and the dispatch of the entry points and the walk over a plan's classes.
+// chud_vbatched_kernel keeps vb_group's lookup written out: through the shared function its instances compile to other machine code.
 #include "chud_step.h"
 #include "vbatch_plan.h"
 
@@ -106,13 +105,7 @@ __device__ __forceinline__ void cb_small(double* R, int64_t ldr, const double* V
   double* const img = s_img + grp * NP * LD;
 
   if (n > 0 && info && *info != 0) n = 0;          // a block that had failed before this call: every predicate below is false for it
-  int nmax = n;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int t = __shfl_xor(nmax, o);
-    nmax = t > nmax ? t : nmax;
-  }
-  nmax = __builtin_amdgcn_readfirstlane(nmax);
+  const int nmax = vb_wave_max(n);
   if (nmax == 0) return;
   if (c == 0) s_first[grp] = 0;
 
@@ -152,7 +145,7 @@ template <int NP, int NKL>
 __global__ __launch_bounds__(64) void chud_vbatched_kernel(CvArgs g) {
   constexpr int G = 64 / NP;
   const int64_t at = (int64_t)blockIdx.x * G + threadIdx.x / NP;
-  int64_t blk = 0, off = 0, ld = 1, row = 0;
+  int64_t blk = 0, off = 0, ld = 1, row = 0;       // vb_group's lookup; cb_small takes the wave's largest n itself, after the info word
   int n = 0;
   if (at < g.count) {
     blk = g.list[at];
@@ -260,31 +253,17 @@ __global__ __launch_bounds__(256) void chud_vbatched_blocked_kernel(CvArgs g) {
 }
 
 // ------------------------------------------------------------------------------------------------ host
-template <int N> using cb_int = std::integral_constant<int, N>;
-
 // NK of the last pass: the smallest of 1, 2, 4, 8, 16 >= its column count (cap_chud_run's choice)
 int cb_last_nk(int64_t k) {
   const int kp = (int)((k - 1) % UK_MAX) + 1;
   return kp <= 1 ? 1 : kp <= 2 ? 2 : kp <= 4 ? 4 : kp <= 8 ? 8 : 16;
 }
 
+// f(NP, NK) with the group size and the last pass's NK as template arguments
 template <class F>
-void cb_with_nk(int nk, F f) {
-  if (nk == 1) f(cb_int<1>{});
-  else if (nk == 2) f(cb_int<2>{});
-  else if (nk == 4) f(cb_int<4>{});
-  else if (nk == 8) f(cb_int<8>{});
-  else f(cb_int<16>{});
+void cb_with(int np, int nk, F f) {
+  vb_with_int<8, 16, 32, 64>(np, [&](auto NP) { vb_with_int<1, 2, 4, 8, 16>(nk, [&](auto NK) { f(NP, NK); }); });
 }
-template <class F>
-void cb_with_np(int np, F f) {
-  if (np == 8) f(cb_int<8>{});
-  else if (np == 16) f(cb_int<16>{});
-  else if (np == 32) f(cb_int<32>{});
-  else f(cb_int<64>{});
-}
-
-int cb_padded(int64_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
 
 }  // namespace
 
@@ -294,17 +273,15 @@ int cap_dcholupdate_batched(int uplo, int sign, int64_t n, int64_t k, double* R,
                             int64_t stride_v, int64_t batch, int* info, void* stream) {
   if ((sign != 1 && sign != -1) || n < 0 || k < 0 || batch < 0) return CAP_ERR_ARG;
   if (n > 0 && k > 0 && batch > 0) {
-    if (!R || !V || ldr < n || ldv < n) return CAP_ERR_ARG;
-    if (batch > 1 && (stride_r < (int64_t)std::min<__int128>((__int128)ldr * n, INT64_MAX) ||
-                      stride_v < (int64_t)std::min<__int128>((__int128)ldv * k, INT64_MAX))) return CAP_ERR_ARG;
+    if (!R || !V || !vb_operand_ok(n, n, ldr, stride_r, batch) || !vb_operand_ok(n, k, ldv, stride_v, batch)) return CAP_ERR_ARG;
   }
   if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrf_batched
   if (n > CB_MAX) return CAP_ERR_UNSUPPORTED;
-  if (n > CB_SMALL && batch > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;     // one 1-D grid, a workgroup per block
+  const int64_t nwg = vb_grid(batch, vb_per_group(vb_class(n)));
+  if (n > CB_SMALL && nwg < 0) return CAP_ERR_UNSUPPORTED;     // a workgroup per block: refused in front of the empty case
   if (n == 0 || k == 0 || batch == 0) return CAP_OK;
-  const int np = cb_padded(n), nkl = cb_last_nk(k);
-  const int64_t nwg = n <= CB_SMALL ? cap_ceil_div(batch, 64 / np) : batch;
-  if (nwg > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;
+  if (nwg < 0) return CAP_ERR_UNSUPPORTED;
+  const int nkl = cb_last_nk(k);
   hipStream_t s = cap_stream(stream);
   if (cap_acc_on()) {
     for (int64_t i = 0; i < batch; i++) {
@@ -318,13 +295,9 @@ int cap_dcholupdate_batched(int uplo, int sign, int64_t n, int64_t k, double* R,
   g.sigma = sign > 0 ? 1.0 : -1.0; g.n = (int)n;
   const dim3 grid((unsigned)nwg);
   if (n <= CB_SMALL) {
-    cb_with_np(np, [&](auto NP) {
-      cb_with_nk(nkl, [&](auto NK) {
-        hipLaunchKernelGGL((chud_batched_kernel<decltype(NP)::value, decltype(NK)::value>), grid, dim3(64), 0, s, g);
-      });
-    });
+    cb_with(vb_padded(n), nkl, [&](auto NP, auto NK) { hipLaunchKernelGGL((chud_batched_kernel<NP(), NK()>), grid, dim3(64), 0, s, g); });
   } else {
-    cb_with_nk(nkl, [&](auto NK) { hipLaunchKernelGGL((chud_batched_blocked_kernel<decltype(NK)::value>), grid, dim3(256), 0, s, g); });
+    vb_with_int<1, 2, 4, 8, 16>(nkl, [&](auto NK) { hipLaunchKernelGGL((chud_batched_blocked_kernel<NK()>), grid, dim3(256), 0, s, g); });
   }
   CAP_HIP(hipGetLastError());
   return CAP_OK;
@@ -342,34 +315,23 @@ int cap_dcholupdate_vbatched(const cap_vbatch_plan* p, int uplo, int sign, int64
   const int nkl = cb_last_nk(k);
   CvArgs g;
   g.rec = p->d_rec; g.R = R; g.V = V; g.ldv = ldv; g.k = k; g.info = info; g.sigma = sign > 0 ? 1.0 : -1.0;
-  for (int cls = 0; cls < VB_CLASSES; cls++) {
-    const std::vector<int64_t>& l = p->list[cls];
-    if (l.empty()) continue;
-    g.list = p->d_list + p->list_at[cls];
-    g.count = (int64_t)l.size();
+  return vb_for_each_class(p, [&](int cls, const int64_t* list, int64_t count, const std::vector<int64_t>& blocks, dim3 grid) {
+    g.list = list;
+    g.count = count;
     if (cap_acc_on()) {
-      cap_acc_r(p->d_rec, 0, p->batch * (int64_t)(sizeof(VbRec) / 8), 1);
-      cap_acc_r(g.list, 0, g.count, 1);
-      for (int64_t b : l) {
+      for (int64_t b : blocks) {
         const VbRec& r = p->rec[(size_t)b];
         cap_acc_rw(R + r.off, r.ld, r.n, r.n, 1);
         cap_acc_r(V + r.row, ldv, r.n, k);
         if (info) cap_acc_rw(info + b, 0, 1, 1, 0, 4);
       }
     }
-    const dim3 grid((unsigned)cap_ceil_div(g.count, vb_per_group(cls)));
     if (cls < 4) {
-      cb_with_np(8 << cls, [&](auto NP) {
-        cb_with_nk(nkl, [&](auto NK) {
-          hipLaunchKernelGGL((chud_vbatched_kernel<decltype(NP)::value, decltype(NK)::value>), grid, dim3(64), 0, s, g);
-        });
-      });
+      cb_with(8 << cls, nkl, [&](auto NP, auto NK) { hipLaunchKernelGGL((chud_vbatched_kernel<NP(), NK()>), grid, dim3(64), 0, s, g); });
     } else {
-      cb_with_nk(nkl, [&](auto NK) { hipLaunchKernelGGL((chud_vbatched_blocked_kernel<decltype(NK)::value>), grid, dim3(256), 0, s, g); });
+      vb_with_int<1, 2, 4, 8, 16>(nkl, [&](auto NK) { hipLaunchKernelGGL((chud_vbatched_blocked_kernel<NK()>), grid, dim3(256), 0, s, g); });
     }
-    CAP_HIP(hipGetLastError());
-  }
-  return CAP_OK;
+  });
 }
 
 }  // extern "C"

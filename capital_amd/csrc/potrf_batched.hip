@@ -28,6 +28,7 @@
 
 #include "common.h"
 #include "batched_small.h"     // the image and the unrolled steps: shared with potrf_vbatched.hip
+#include "vbatch_plan.h"       // the family's host arithmetic: padded size, grid limit, dispatch, operand rule
 
 namespace {
 
@@ -116,16 +117,14 @@ __global__ __launch_bounds__(64) void potrs_batched_kernel(PbSolveArgs g) {
   }
 }
 
-int pb_padded(int64_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
-
 }  // namespace
 
 int cap_potrf_batched_launch(int64_t n, double* A, int64_t lda, int64_t stride_a, int64_t batch, int* info, double* logdet, hipStream_t s) {
   if (n <= 0 || batch <= 0) return CAP_OK;
   if (n > PB_MAX) return CAP_ERR_UNSUPPORTED;
-  const int np = pb_padded(n);
-  const int64_t nwg = cap_ceil_div(batch, 64 / np);
-  if (nwg > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;      // one 1-D grid
+  const int np = vb_padded(n);
+  const int64_t nwg = vb_grid(batch, 64 / np);
+  if (nwg < 0) return CAP_ERR_UNSUPPORTED;
   PbArgs g;
   g.A = A; g.lda = lda; g.stride_a = stride_a; g.batch = batch; g.info = info; g.logdet = logdet; g.n = (int)n;
   if (cap_acc_on()) {
@@ -133,11 +132,7 @@ int cap_potrf_batched_launch(int64_t n, double* A, int64_t lda, int64_t stride_a
     if (info) cap_acc_w(info, 0, batch, 1, 0, 4);
     if (logdet) cap_acc_w(logdet, 0, batch, 1);
   }
-  const dim3 grid((unsigned)nwg), block(64);
-  if (np == 8) hipLaunchKernelGGL(potrf_batched_kernel<8>, grid, block, 0, s, g);
-  else if (np == 16) hipLaunchKernelGGL(potrf_batched_kernel<16>, grid, block, 0, s, g);
-  else if (np == 32) hipLaunchKernelGGL(potrf_batched_kernel<32>, grid, block, 0, s, g);
-  else hipLaunchKernelGGL(potrf_batched_kernel<64>, grid, block, 0, s, g);
+  vb_with_int<8, 16, 32, 64>(np, [&](auto NP) { hipLaunchKernelGGL(potrf_batched_kernel<NP()>, dim3((unsigned)nwg), dim3(64), 0, s, g); });
   CAP_HIP(hipGetLastError());
   return CAP_OK;
 }
@@ -146,9 +141,9 @@ int cap_potrs_batched_launch(int64_t n, int64_t nrhs, const double* R, int64_t l
                              int64_t batch, const int* info, hipStream_t s) {
   if (n <= 0 || batch <= 0 || nrhs <= 0) return CAP_OK;
   if (n > PB_MAX) return CAP_ERR_UNSUPPORTED;
-  const int np = pb_padded(n);
-  const int64_t nwg = cap_ceil_div(batch, 64 / np);
-  if (nwg > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;
+  const int np = vb_padded(n);
+  const int64_t nwg = vb_grid(batch, 64 / np);
+  if (nwg < 0) return CAP_ERR_UNSUPPORTED;
   PbSolveArgs g;
   g.R = R; g.ldr = ldr; g.stride_r = stride_r; g.B = B; g.ldb = ldb; g.stride_b = stride_b; g.batch = batch; g.nrhs = nrhs; g.info = info;
   g.n = (int)n;
@@ -157,11 +152,7 @@ int cap_potrs_batched_launch(int64_t n, int64_t nrhs, const double* R, int64_t l
     cap_acc_rw(B, 0, (batch - 1) * stride_b + (nrhs - 1) * ldb + n, 1);
     if (info) cap_acc_r(info, 0, batch, 1, 0, 4);
   }
-  const dim3 grid((unsigned)nwg), block(64);
-  if (np == 8) hipLaunchKernelGGL(potrs_batched_kernel<8>, grid, block, 0, s, g);
-  else if (np == 16) hipLaunchKernelGGL(potrs_batched_kernel<16>, grid, block, 0, s, g);
-  else if (np == 32) hipLaunchKernelGGL(potrs_batched_kernel<32>, grid, block, 0, s, g);
-  else hipLaunchKernelGGL(potrs_batched_kernel<64>, grid, block, 0, s, g);
+  vb_with_int<8, 16, 32, 64>(np, [&](auto NP) { hipLaunchKernelGGL(potrs_batched_kernel<NP()>, dim3((unsigned)nwg), dim3(64), 0, s, g); });
   CAP_HIP(hipGetLastError());
   return CAP_OK;
 }
@@ -171,8 +162,7 @@ extern "C" {
 int cap_dpotrf_batched(int uplo, int64_t n, double* A, int64_t lda, int64_t stride_a, int64_t batch, int* info, double* logdet, void* stream) {
   if (n < 0 || batch < 0) return CAP_ERR_ARG;
   if (n > 0 && batch > 0 && !A) return CAP_ERR_ARG;
-  if (lda < n) return CAP_ERR_ARG;
-  if (batch > 1 && stride_a < lda * n) return CAP_ERR_ARG;
+  if (!vb_operand_ok(n, n, lda, stride_a, batch)) return CAP_ERR_ARG;
   if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrf
   if (n > PB_MAX) return CAP_ERR_UNSUPPORTED;
   return cap_potrf_batched_launch(n, A, lda, stride_a, batch, info, logdet, cap_stream(stream));
@@ -182,8 +172,7 @@ int cap_dpotrs_batched(int uplo, int64_t n, int64_t nrhs, const double* R, int64
                        int64_t stride_b, int64_t batch, const int* info, void* stream) {
   if (n < 0 || batch < 0 || nrhs < 0) return CAP_ERR_ARG;
   if (n > 0 && batch > 0 && (!R || !B)) return CAP_ERR_ARG;
-  if (ldr < n || ldb < n) return CAP_ERR_ARG;
-  if (batch > 1 && (stride_r < ldr * n || stride_b < ldb * nrhs)) return CAP_ERR_ARG;
+  if (!vb_operand_ok(n, n, ldr, stride_r, batch) || !vb_operand_ok(n, nrhs, ldb, stride_b, batch)) return CAP_ERR_ARG;
   if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;
   if (n > PB_MAX) return CAP_ERR_UNSUPPORTED;
   return cap_potrs_batched_launch(n, nrhs, R, ldr, stride_r, B, ldb, stride_b, batch, info, cap_stream(stream));

@@ -31,6 +31,7 @@
 // memory (every element once) and Y from LDS.  An MFMA output column depends on its own input column only: a dead column never feeds a live one
 // and a column's bits do not depend on which of the 16 places it takes.
 #include "batched_blocked.h"   // the per-block bodies of the two kernels below: shared with potrf_vbatched.hip
+#include "vbatch_plan.h"       // the family's host arithmetic: grid limit, dispatch, operand rule
 
 namespace {
 
@@ -51,14 +52,13 @@ int cap_dpotrf_batched_blocked(int uplo, int64_t n, double* A, int64_t lda, int6
                                void* stream) {
   if (n < 0 || batch < 0) return CAP_ERR_ARG;
   if (n > 0 && batch > 0 && !A) return CAP_ERR_ARG;
-  if (lda < n) return CAP_ERR_ARG;
-  if (batch > 1 && stride_a < lda * n) return CAP_ERR_ARG;
+  if (!vb_operand_ok(n, n, lda, stride_a, batch)) return CAP_ERR_ARG;
   if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrf_batched
   if (n > BB_MAX) return CAP_ERR_UNSUPPORTED;
   if (n == 0 || batch == 0) return CAP_OK;
   hipStream_t s = cap_stream(stream);
   if (n <= BB_SMALL) return cap_potrf_batched_launch(n, A, lda, stride_a, batch, info, logdet, s);
-  if (batch > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;  // one 1-D grid, a workgroup per block
+  if (vb_grid(batch, 1) < 0) return CAP_ERR_UNSUPPORTED;  // a workgroup per block
   BbArgs g;
   g.A = A; g.lda = lda; g.stride_a = stride_a; g.info = info; g.logdet = logdet; g.n = (int)n;
   if (cap_acc_on()) {
@@ -66,10 +66,9 @@ int cap_dpotrf_batched_blocked(int uplo, int64_t n, double* A, int64_t lda, int6
     if (info) cap_acc_w(info, 0, batch, 1, 0, 4);
     if (logdet) cap_acc_w(logdet, 0, batch, 1);
   }
-  const dim3 grid((unsigned)batch);
-  if (n <= 2 * BB_NB) hipLaunchKernelGGL(potrf_batched_blocked_kernel<2>, grid, dim3(64 * bb_factor_waves(2)), 0, s, g);
-  else if (n <= 3 * BB_NB) hipLaunchKernelGGL(potrf_batched_blocked_kernel<3>, grid, dim3(64 * bb_factor_waves(3)), 0, s, g);
-  else hipLaunchKernelGGL(potrf_batched_blocked_kernel<4>, grid, dim3(64 * bb_factor_waves(4)), 0, s, g);
+  vb_with_int<2, 3, 4>((int)cap_ceil_div(n, BB_NB), [&](auto NBLK) {
+    hipLaunchKernelGGL(potrf_batched_blocked_kernel<NBLK()>, dim3((unsigned)batch), dim3(64 * bb_factor_waves(NBLK())), 0, s, g);
+  });
   CAP_HIP(hipGetLastError());
   return CAP_OK;
 }
@@ -78,14 +77,13 @@ int cap_dpotrs_batched_blocked(int uplo, int64_t n, int64_t nrhs, const double* 
                                int64_t stride_b, int64_t batch, const int* info, void* stream) {
   if (n < 0 || batch < 0 || nrhs < 0) return CAP_ERR_ARG;
   if (n > 0 && batch > 0 && (!R || !B)) return CAP_ERR_ARG;
-  if (ldr < n || ldb < n) return CAP_ERR_ARG;
-  if (batch > 1 && (stride_r < ldr * n || stride_b < ldb * nrhs)) return CAP_ERR_ARG;
+  if (!vb_operand_ok(n, n, ldr, stride_r, batch) || !vb_operand_ok(n, nrhs, ldb, stride_b, batch)) return CAP_ERR_ARG;
   if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;
   if (n > BB_MAX) return CAP_ERR_UNSUPPORTED;
   if (n == 0 || batch == 0 || nrhs == 0) return CAP_OK;
   hipStream_t s = cap_stream(stream);
   if (n <= BB_SMALL) return cap_potrs_batched_launch(n, nrhs, R, ldr, stride_r, B, ldb, stride_b, batch, info, s);
-  if (batch > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;
+  if (vb_grid(batch, 1) < 0) return CAP_ERR_UNSUPPORTED;
   BbSolveArgs g;
   g.R = R; g.ldr = ldr; g.stride_r = stride_r; g.B = B; g.ldb = ldb; g.stride_b = stride_b; g.nrhs = nrhs; g.info = info; g.n = (int)n;
   if (cap_acc_on()) {

@@ -8,7 +8,7 @@
 // a wave have neighbouring sizes.  A call is ONE launch per non-empty class on the caller's stream (seven at most) and nothing else: no
 // scratch, no allocation, no memset, no atomics, no helper stream, no host synchronisation; nothing between workgroups.
 //
-// THE ARITHMETIC is that of potrf_batched.hip / potrf_batched_blocked.hip / potri_batched.hip, from the shared headers: every block gets, bit
+// THE ARITHMETIC is that of the fixed-size entries, from the shared headers batched_small.h / batched_blocked.h / batched_inverse.h: every block gets, bit
 // for bit, what the fixed-size entry writes for it with n = n_i and batch = 1 - info and logdet included - whichever blocks share its wave, its
 // class list or the batch.
 //   n_i > 64: the workgroup looks its block up (blockIdx.x -> class list -> record) and runs the fixed-size kernel's body on it; n is uniform
@@ -24,6 +24,9 @@
 //     becomes a lane mask and every lane executes exactly the fixed-size sequence for its own block.  The product's row sums take the
 //     group's own n for their chunks (a padded chunk would add +0 products, which is not the identity on a sum that underflowed to -0).
 //     A wave's dead groups (the tail of a class) have n = 0: every predicate is false for them.
+// SHARED (vbatch_plan.h): the plan's layout, the walk over its classes (vb_for_each_class), a lane group's lookup of its block (vb_group,
+// vb_load_upper) and the dispatch of a runtime class to a kernel instance (vb_with_int) - what trsm_batched.hip, cholupdate_batched.hip and
+// syrk_batched.hip run on too.
 #include <algorithm>
 #include <new>
 #include <vector>
@@ -32,7 +35,7 @@
 #include "batched_blocked.h"
 #include "batched_inverse.h"
 #include "capital_amd.h"
-#include "vbatch_plan.h"   // VbRec, cap_vbatch_plan, vb_per_group: shared with cholupdate_batched.hip
+#include "vbatch_plan.h"   // the plan, its walk and the lane group's block lookup (vb_group, vb_load_upper)
 
 namespace {
 
@@ -46,41 +49,6 @@ struct VbArgs {                        // one class of one call
   double* B; int64_t ldb, nrhs;
   int fill;
 };
-
-// what a lane group of a wave-per-blocks kernel works on: its block (n = 0: none) and the largest n of its wave
-struct VbGroup {
-  int64_t blk, off, ld, row;
-  int n, nmax;
-};
-
-template <int NP>
-__device__ __forceinline__ VbGroup vb_group(const VbArgs& g) {
-  constexpr int G = 64 / NP;
-  const int64_t at = (int64_t)blockIdx.x * G + threadIdx.x / NP;
-  VbGroup v;
-  v.blk = 0; v.off = 0; v.ld = 1; v.row = 0; v.n = 0;
-  if (at < g.count) {
-    v.blk = g.list[at];
-    const VbRec r = g.rec[v.blk];
-    v.off = r.off; v.ld = r.ld; v.row = r.row; v.n = (int)r.n;
-  }
-  int m = v.n;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int t = __shfl_xor(m, o);
-    m = t > m ? t : m;
-  }
-  v.nmax = __builtin_amdgcn_readfirstlane(m);
-  return v;
-}
-
-// upper triangle of the group's n x n block -> its image (pb_load_upper with the group's own n as a lane predicate)
-template <int NP>
-__device__ __forceinline__ void vb_load_upper(const double* M, int64_t ld, int n, int nmax, int r, double* s) {
-#pragma unroll 8
-  for (int c = 0; c < nmax; c++)
-    if (r <= c && c < n) s[PbImg<NP>::at(r, c)] = M[r + (int64_t)c * ld];
-}
 
 // pb_factor_step with the wave's nmax in the uniform branches and the group's n in the pivot decision
 template <int NP>
@@ -145,12 +113,12 @@ __global__ __launch_bounds__(64) void potrf_vbatched_kernel(VbArgs g) {
   __shared__ double s_img[G * Img::SIZE];
   __shared__ double s_log[64];
   const int lane = threadIdx.x, grp = lane / NP, c = lane % NP;
-  const VbGroup v = vb_group<NP>(g);
+  const VbGroup v = vb_group<NP>(g.rec, g.list, g.count);
   const int n = v.n, nmax = v.nmax;
   double* A = g.A + v.off;
   double* s = s_img + grp * Img::SIZE;
 
-  vb_load_upper<NP>(A, v.ld, n, nmax, c, s);
+  vb_load_upper<Img>(A, v.ld, n, nmax, c, s);
   __syncthreads();
   double a[NP];
 #pragma unroll
@@ -191,11 +159,11 @@ __global__ __launch_bounds__(64) void potrs_vbatched_kernel(VbArgs g) {
   using Img = PbImg<NP>;
   __shared__ double s_img[G * Img::SIZE];
   const int lane = threadIdx.x, grp = lane / NP, k = lane % NP;
-  const VbGroup v = vb_group<NP>(g);
+  const VbGroup v = vb_group<NP>(g.rec, g.list, g.count);
   const int n = v.n, nmax = v.nmax;
   const double* s = s_img + grp * Img::SIZE;
 
-  vb_load_upper<NP>(g.A + v.off, v.ld, n, nmax, k, s_img + grp * Img::SIZE);
+  vb_load_upper<Img>(g.A + v.off, v.ld, n, nmax, k, s_img + grp * Img::SIZE);
   const bool bad = g.info && n > 0 && g.info[v.blk] != 0;
   __syncthreads();
 
@@ -231,7 +199,7 @@ __global__ __launch_bounds__(64) void potri_vbatched_kernel(VbArgs g) {
   using Img = PiImg<NP>;
   __shared__ double s_img[G * Img::SIZE];
   const int lane = threadIdx.x, grp = lane / NP, c = lane % NP;
-  const VbGroup v = vb_group<NP>(g);
+  const VbGroup v = vb_group<NP>(g.rec, g.list, g.count);
   const int n = v.n, nmax = v.nmax;
   const int64_t ld = v.ld;
   double* A = g.A + v.off;
@@ -298,60 +266,32 @@ __global__ __launch_bounds__(64 * pi_waves(NBLK)) void potri_vbatched_blocked_ke
   pi_blocked_block<NBLK>(g.A + r.off, r.ld, (int)r.n, g.info, blk, 1, g.fill);
 }
 
-int64_t vb_clip(__int128 v) { return v > (__int128)INT64_MAX ? INT64_MAX : (int64_t)v; }
-int vb_class(int64_t n) { return n <= 8 ? 0 : n <= 16 ? 1 : n <= 32 ? 2 : n <= 64 ? 3 : n <= 128 ? 4 : n <= 192 ? 5 : 6; }
-
 enum { VB_FACTOR, VB_SOLVE, VB_INVERSE };
 
-void vb_launch(int op, int cls, unsigned grid, hipStream_t s, const VbArgs& g) {
-  const dim3 gr(grid), wave(64);
-#define VB_SMALL(K, NP) hipLaunchKernelGGL((K<NP>), gr, wave, 0, s, g)
-#define VB_BLOCKED(K, NBLK, W) hipLaunchKernelGGL((K<NBLK>), gr, dim3(64 * W(NBLK)), 0, s, g)
+void vb_launch(int op, int cls, dim3 grid, hipStream_t s, const VbArgs& g) {
+  const int np = 8 << cls, nblk = cls - 2;       // the template argument of the class: NP up to class 3, NBLK above
   if (op == VB_FACTOR) {
-    if (cls == 0) VB_SMALL(potrf_vbatched_kernel, 8);
-    else if (cls == 1) VB_SMALL(potrf_vbatched_kernel, 16);
-    else if (cls == 2) VB_SMALL(potrf_vbatched_kernel, 32);
-    else if (cls == 3) VB_SMALL(potrf_vbatched_kernel, 64);
-    else if (cls == 4) VB_BLOCKED(potrf_vbatched_blocked_kernel, 2, bb_factor_waves);
-    else if (cls == 5) VB_BLOCKED(potrf_vbatched_blocked_kernel, 3, bb_factor_waves);
-    else VB_BLOCKED(potrf_vbatched_blocked_kernel, 4, bb_factor_waves);
+    if (cls < 4) vb_with_int<8, 16, 32, 64>(np, [&](auto NP) { hipLaunchKernelGGL(potrf_vbatched_kernel<NP()>, grid, dim3(64), 0, s, g); });
+    else vb_with_int<2, 3, 4>(nblk, [&](auto NB) { hipLaunchKernelGGL(potrf_vbatched_blocked_kernel<NB()>, grid, dim3(64 * bb_factor_waves(NB())), 0, s, g); });
   } else if (op == VB_SOLVE) {
-    if (cls == 0) VB_SMALL(potrs_vbatched_kernel, 8);
-    else if (cls == 1) VB_SMALL(potrs_vbatched_kernel, 16);
-    else if (cls == 2) VB_SMALL(potrs_vbatched_kernel, 32);
-    else if (cls == 3) VB_SMALL(potrs_vbatched_kernel, 64);
-    else hipLaunchKernelGGL(potrs_vbatched_blocked_kernel, gr, dim3(BB_THREADS), 0, s, g);
+    if (cls < 4) vb_with_int<8, 16, 32, 64>(np, [&](auto NP) { hipLaunchKernelGGL(potrs_vbatched_kernel<NP()>, grid, dim3(64), 0, s, g); });
+    else hipLaunchKernelGGL(potrs_vbatched_blocked_kernel, grid, dim3(BB_THREADS), 0, s, g);
   } else {
-    if (cls == 0) VB_SMALL(potri_vbatched_kernel, 8);
-    else if (cls == 1) VB_SMALL(potri_vbatched_kernel, 16);
-    else if (cls == 2) VB_SMALL(potri_vbatched_kernel, 32);
-    else if (cls == 3) VB_SMALL(potri_vbatched_kernel, 64);
-    else if (cls == 4) VB_BLOCKED(potri_vbatched_blocked_kernel, 2, pi_waves);
-    else if (cls == 5) VB_BLOCKED(potri_vbatched_blocked_kernel, 3, pi_waves);
-    else VB_BLOCKED(potri_vbatched_blocked_kernel, 4, pi_waves);
+    if (cls < 4) vb_with_int<8, 16, 32, 64>(np, [&](auto NP) { hipLaunchKernelGGL(potri_vbatched_kernel<NP()>, grid, dim3(64), 0, s, g); });
+    else vb_with_int<2, 3, 4>(nblk, [&](auto NB) { hipLaunchKernelGGL(potri_vbatched_blocked_kernel<NB()>, grid, dim3(64 * pi_waves(NB())), 0, s, g); });
   }
-#undef VB_SMALL
-#undef VB_BLOCKED
 }
-
-}  // namespace
-
-namespace {
 
 // the launches of one call: one per non-empty class, in class order
 int vb_run(int op, const cap_vbatch_plan* p, VbArgs g, hipStream_t s) {
   if (p->nonempty == 0) return CAP_OK;
   if (p->device < 0) return CAP_ERR_HIP;
   g.rec = p->d_rec;
-  for (int cls = 0; cls < VB_CLASSES; cls++) {
-    const std::vector<int64_t>& l = p->list[cls];
-    if (l.empty()) continue;
-    g.list = p->d_list + p->list_at[cls];
-    g.count = (int64_t)l.size();
+  return vb_for_each_class(p, [&](int cls, const int64_t* list, int64_t count, const std::vector<int64_t>& blocks, dim3 grid) {
+    g.list = list;
+    g.count = count;
     if (cap_acc_on()) {
-      cap_acc_r(p->d_rec, 0, p->batch * (int64_t)(sizeof(VbRec) / 8), 1);
-      cap_acc_r(g.list, 0, g.count, 1);
-      for (int64_t b : l) {
+      for (int64_t b : blocks) {
         const VbRec& r = p->rec[b];
         if (op == VB_FACTOR) {
           cap_acc_rw(g.A + r.off, r.ld, r.n, r.n, 1);
@@ -367,10 +307,8 @@ int vb_run(int op, const cap_vbatch_plan* p, VbArgs g, hipStream_t s) {
         }
       }
     }
-    vb_launch(op, cls, (unsigned)cap_ceil_div(g.count, vb_per_group(cls)), s, g);
-    CAP_HIP(hipGetLastError());
-  }
-  return CAP_OK;
+    vb_launch(op, cls, grid, s, g);
+  });
 }
 
 }  // namespace
@@ -415,7 +353,7 @@ int cap_vbatch_plan_create(int64_t batch, const int64_t* n, const int64_t* ld, c
   for (int cls = 0; cls < VB_CLASSES; cls++) {
     std::vector<int64_t>& l = p->list[cls];
     std::stable_sort(l.begin(), l.end(), [&](int64_t a, int64_t b) { return p->rec[(size_t)a].n < p->rec[(size_t)b].n; });
-    if (cap_ceil_div((int64_t)l.size(), vb_per_group(cls)) > 0x7fffffffLL) { delete p; return CAP_ERR_UNSUPPORTED; }   // one 1-D grid per class
+    if (vb_grid((int64_t)l.size(), vb_per_group(cls)) < 0) { delete p; return CAP_ERR_UNSUPPORTED; }   // one 1-D grid per class
     p->list_at[cls] = at;
     at += (int64_t)l.size();
     p->nonempty += l.empty() ? 0 : 1;

@@ -30,6 +30,7 @@
 // Every block sees the same instruction sequence on its own data: its bits depend on (n, its data, fill) only.  All global accesses are
 // 8-byte ones: one load path whatever the alignment.  Divisions are correctly rounded (no reciprocal estimates).
 #include "batched_inverse.h"   // the steps for n <= 64 and the per-block body for n > 64: shared with potrf_vbatched.hip
+#include "vbatch_plan.h"       // the family's host arithmetic: padded size, grid limit, dispatch, operand rule
 
 namespace {
 
@@ -94,31 +95,18 @@ __global__ __launch_bounds__(64 * pi_waves(NBLK)) void potri_batched_blocked_ker
   pi_blocked_block<NBLK>(g.A + (int64_t)blockIdx.x * g.stride, g.ld, g.n, g.info, blockIdx.x, g.potri, g.fill);
 }
 
-int pi_padded(int64_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
-
-template <bool POTRI>
-void pi_launch_small(int np, dim3 grid, hipStream_t s, const PiArgs& g) {
-  const dim3 block(64);
-  if (np == 8) hipLaunchKernelGGL((potri_batched_kernel<8, POTRI>), grid, block, 0, s, g);
-  else if (np == 16) hipLaunchKernelGGL((potri_batched_kernel<16, POTRI>), grid, block, 0, s, g);
-  else if (np == 32) hipLaunchKernelGGL((potri_batched_kernel<32, POTRI>), grid, block, 0, s, g);
-  else hipLaunchKernelGGL((potri_batched_kernel<64, POTRI>), grid, block, 0, s, g);
-}
-
 // the two entries: potri = 0 the triangular inverse, 1 the SPD inverse from the factor
 int pi_run(int potri, int uplo, int64_t n, double* T, int64_t ld, int64_t stride, int64_t batch, const int* info, int fill, void* stream) {
   if (n < 0 || batch < 0) return CAP_ERR_ARG;
   if (n > 0 && batch > 0 && !T) return CAP_ERR_ARG;
-  if (ld < n) return CAP_ERR_ARG;
-  if (batch > 1 && stride < ld * n) return CAP_ERR_ARG;
+  if (!vb_operand_ok(n, n, ld, stride, batch)) return CAP_ERR_ARG;
   if (fill != 0 && fill != 1) return CAP_ERR_ARG;
   if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrf_batched
   if (n > PI_MAX) return CAP_ERR_UNSUPPORTED;
-  if (n > PI_SMALL && batch > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;     // one 1-D grid, a workgroup per block
+  const int64_t nwg = vb_grid(batch, vb_per_group(vb_class(n)));
+  if (n > PI_SMALL && nwg < 0) return CAP_ERR_UNSUPPORTED;     // a workgroup per block: refused in front of the empty case
   if (n == 0 || batch == 0) return CAP_OK;
-  const int np = pi_padded(n);
-  const int64_t nwg = n <= PI_SMALL ? cap_ceil_div(batch, 64 / np) : batch;
-  if (nwg > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;
+  if (nwg < 0) return CAP_ERR_UNSUPPORTED;
   hipStream_t s = cap_stream(stream);
   if (cap_acc_on()) {
     for (int64_t i = 0; i < batch; i++) cap_acc_rw(T + i * stride, ld, n, n, fill ? 0 : 1);
@@ -128,14 +116,14 @@ int pi_run(int potri, int uplo, int64_t n, double* T, int64_t ld, int64_t stride
   if (n <= PI_SMALL) {
     PiArgs g;
     g.A = T; g.ld = ld; g.stride = stride; g.batch = batch; g.info = info; g.n = (int)n; g.fill = fill;
-    if (potri) pi_launch_small<true>(np, grid, s, g);
-    else pi_launch_small<false>(np, grid, s, g);
+    if (potri) vb_with_int<8, 16, 32, 64>(vb_padded(n), [&](auto NP) { hipLaunchKernelGGL((potri_batched_kernel<NP(), true>), grid, dim3(64), 0, s, g); });
+    else vb_with_int<8, 16, 32, 64>(vb_padded(n), [&](auto NP) { hipLaunchKernelGGL((potri_batched_kernel<NP(), false>), grid, dim3(64), 0, s, g); });
   } else {
     PiBlkArgs g;
     g.A = T; g.ld = ld; g.stride = stride; g.info = info; g.n = (int)n; g.potri = potri; g.fill = fill;
-    if (n <= 2 * PI_NB) hipLaunchKernelGGL(potri_batched_blocked_kernel<2>, grid, dim3(64 * pi_waves(2)), 0, s, g);
-    else if (n <= 3 * PI_NB) hipLaunchKernelGGL(potri_batched_blocked_kernel<3>, grid, dim3(64 * pi_waves(3)), 0, s, g);
-    else hipLaunchKernelGGL(potri_batched_blocked_kernel<4>, grid, dim3(64 * pi_waves(4)), 0, s, g);
+    vb_with_int<2, 3, 4>((int)cap_ceil_div(n, PI_NB), [&](auto NBLK) {
+      hipLaunchKernelGGL(potri_batched_blocked_kernel<NBLK()>, grid, dim3(64 * pi_waves(NBLK())), 0, s, g);
+    });
   }
   CAP_HIP(hipGetLastError());
   return CAP_OK;

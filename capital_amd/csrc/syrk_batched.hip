@@ -32,7 +32,9 @@
 // either layout gives the same bits.  4. ELEMENT INDEPENDENCE: c_rc is a function of rows r and c of V (and k, alpha, beta, c_old, shift)
 // alone, the same on the wave path and on the workgroup path: every output element is its own chain from a zero accumulator, and the
 // epilogue is elementwise.  1 - 3 hold by construction given 4; 4 rests on the MFMA computing every element of a tile alike.
-#include <algorithm>
+// SHARED (vbatch_plan.h): the argument rules, the grid and the dispatch of the entry points, the walk over a plan's classes and the wave's
+// largest n (vb_wave_max).  sb_block keeps its own lookup: one function serves the fixed-size and the plan kernels (PLAN) and returns the
+// block as pointers into V and C, which vb_group does not know.
 #include <vector>
 
 #include "batched_blocked.h"
@@ -231,14 +233,7 @@ __device__ __forceinline__ void sb_wave(const SbArgs& g) {
     m = b[s].n > m ? b[s].n : m;
   }
   int nmax = g.n;
-  if constexpr (PLAN) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const int t = __shfl_xor(m, o);
-      m = t > m ? t : m;
-    }
-    nmax = __builtin_amdgcn_readfirstlane(m);
-  }
+  if constexpr (PLAN) nmax = vb_wave_max(m);
   sb_macro<NP, TRANS, true, 4>(g, b, 0, 0, nmax, lr, kg);
 }
 
@@ -273,41 +268,32 @@ __global__ __launch_bounds__(BB_THREADS) void syrk_vbatched_blocked_kernel(SbArg
 
 // ------------------------------------------------------------------------------------------------ host
 static_assert((BB_WAVES & (BB_WAVES - 1)) == 0, "the macro tiles are dealt with a mask");
-template <int N> using sb_int = std::integral_constant<int, N>;
 
+// f(NP, TRANS) with the group size and the layout of V as template arguments
 template <class F>
 void sb_with(int np, int trans, F f) {
-  auto t = [&](auto NP) {
+  vb_with_int<8, 16, 32, 64>(np, [&](auto NP) {
     if (trans == CAP_TRANS) f(NP, std::true_type{});
     else f(NP, std::false_type{});
-  };
-  if (np == 8) t(sb_int<8>{});
-  else if (np == 16) t(sb_int<16>{});
-  else if (np == 32) t(sb_int<32>{});
-  else t(sb_int<64>{});
+  });
 }
-
-int sb_padded(int64_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
-int64_t sb_mul_clip(int64_t a, int64_t b) { return (int64_t)std::min<__int128>((__int128)a * b, INT64_MAX); }
 
 int sb_fixed(int uplo, int trans, int64_t n, int64_t k, double alpha, const double* V, int64_t ldv, int64_t stride_v, double beta, double* C,
              int64_t ldc, int64_t stride_c, const double* shift, int fill, int64_t batch, hipStream_t s) {
   if ((trans != CAP_NOTRANS && trans != CAP_TRANS) || n < 0 || k < 0 || batch < 0 || (fill != 0 && fill != 1)) return CAP_ERR_ARG;
   if (!C && n > 0 && batch > 0) return CAP_ERR_ARG;
   if (!V && n > 0 && k > 0 && batch > 0 && alpha != 0.0) return CAP_ERR_ARG;
-  if (ldc < n) return CAP_ERR_ARG;
-  if (ldv < (trans == CAP_TRANS ? k : n)) return CAP_ERR_ARG;
-  if (batch > 1 && (stride_c < sb_mul_clip(ldc, n) || stride_v < sb_mul_clip(ldv, trans == CAP_TRANS ? n : k))) return CAP_ERR_ARG;
+  const int64_t vrows = trans == CAP_TRANS ? k : n, vcols = trans == CAP_TRANS ? n : k;
+  if (!vb_operand_ok(n, n, ldc, stride_c, batch) || !vb_operand_ok(vrows, vcols, ldv, stride_v, batch)) return CAP_ERR_ARG;
   if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;      // as the other batched entries
   if (n > SB_MAX) return CAP_ERR_UNSUPPORTED;
-  const int np = sb_padded(n);
-  const int64_t nwg = n <= BB_SMALL ? cap_ceil_div(batch, 64 / np) : batch;
-  if (nwg > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;      // one 1-D grid
+  const int64_t nwg = vb_grid(batch, vb_per_group(vb_class(n)));
+  if (nwg < 0) return CAP_ERR_UNSUPPORTED;
   if (n == 0 || batch == 0) return CAP_OK;
   const int64_t keff = alpha == 0.0 ? 0 : k;
   if (cap_acc_on()) {
     for (int64_t i = 0; i < batch; i++) {
-      if (keff > 0) cap_acc_r(V + i * stride_v, ldv, trans == CAP_TRANS ? k : n, trans == CAP_TRANS ? n : k);
+      if (keff > 0) cap_acc_r(V + i * stride_v, ldv, vrows, vcols);
       if (beta == 0.0) cap_acc_w(C + i * stride_c, ldc, n, n, fill ? 0 : 1);
       else cap_acc_rw(C + i * stride_c, ldc, n, n, fill ? 0 : 1);
     }
@@ -317,9 +303,9 @@ int sb_fixed(int uplo, int trans, int64_t n, int64_t k, double alpha, const doub
   g.V = V; g.ldv = ldv; g.stride_v = stride_v; g.C = C; g.ldc = ldc; g.stride_c = stride_c; g.shift = shift; g.alpha = alpha; g.beta = beta;
   g.batch = batch; g.k = keff; g.n = (int)n; g.fill = fill;
   const dim3 grid((unsigned)nwg);
-  sb_with(np, trans, [&](auto NP, auto TR) {
-    if (n <= BB_SMALL) hipLaunchKernelGGL((syrk_batched_kernel<decltype(NP)::value, decltype(TR)::value>), grid, dim3(64), 0, s, g);
-    else if (decltype(NP)::value == 64) hipLaunchKernelGGL((syrk_batched_blocked_kernel<decltype(TR)::value>), grid, dim3(BB_THREADS), 0, s, g);
+  sb_with(vb_padded(n), trans, [&](auto NP, auto TR) {
+    if (n <= BB_SMALL) hipLaunchKernelGGL((syrk_batched_kernel<NP(), TR()>), grid, dim3(64), 0, s, g);
+    else if (NP() == 64) hipLaunchKernelGGL((syrk_batched_blocked_kernel<TR()>), grid, dim3(BB_THREADS), 0, s, g);
   });
   CAP_HIP(hipGetLastError());
   return CAP_OK;
@@ -337,15 +323,11 @@ int sb_plan(const cap_vbatch_plan* p, int uplo, int trans, int64_t k, double alp
   const int64_t keff = alpha == 0.0 ? 0 : k;
   SbArgs g = {};
   g.V = V; g.ldv = ldv; g.C = C; g.shift = shift; g.alpha = alpha; g.beta = beta; g.k = keff; g.fill = fill; g.rec = p->d_rec;
-  for (int cls = 0; cls < VB_CLASSES; cls++) {
-    const std::vector<int64_t>& l = p->list[cls];
-    if (l.empty()) continue;
-    g.list = p->d_list + p->list_at[cls];
-    g.count = (int64_t)l.size();
+  return vb_for_each_class(p, [&](int cls, const int64_t* list, int64_t count, const std::vector<int64_t>& blocks, dim3 grid) {
+    g.list = list;
+    g.count = count;
     if (cap_acc_on()) {
-      cap_acc_r(p->d_rec, 0, p->batch * (int64_t)(sizeof(VbRec) / 8), 1);
-      cap_acc_r(g.list, 0, g.count, 1);
-      for (int64_t b : l) {
+      for (int64_t b : blocks) {
         const VbRec& r = p->rec[(size_t)b];
         if (keff > 0) {
           if (trans == CAP_TRANS) cap_acc_r(V + r.row * ldv, ldv, k, r.n);
@@ -356,14 +338,11 @@ int sb_plan(const cap_vbatch_plan* p, int uplo, int trans, int64_t k, double alp
         if (shift) cap_acc_r(shift + b, 0, 1, 1);
       }
     }
-    const dim3 grid((unsigned)cap_ceil_div(g.count, vb_per_group(cls)));
     sb_with(cls < 4 ? 8 << cls : 64, trans, [&](auto NP, auto TR) {
-      if (cls < 4) hipLaunchKernelGGL((syrk_vbatched_kernel<decltype(NP)::value, decltype(TR)::value>), grid, dim3(64), 0, s, g);
-      else if (decltype(NP)::value == 64) hipLaunchKernelGGL((syrk_vbatched_blocked_kernel<decltype(TR)::value>), grid, dim3(BB_THREADS), 0, s, g);
+      if (cls < 4) hipLaunchKernelGGL((syrk_vbatched_kernel<NP(), TR()>), grid, dim3(64), 0, s, g);
+      else if (NP() == 64) hipLaunchKernelGGL((syrk_vbatched_blocked_kernel<TR()>), grid, dim3(BB_THREADS), 0, s, g);
     });
-    CAP_HIP(hipGetLastError());
-  }
-  return CAP_OK;
+  });
 }
 
 }  // namespace

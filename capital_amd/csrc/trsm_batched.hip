@@ -19,7 +19,7 @@
 //
 // 64 < n <= 256: bb_solve_block's structure (batched_blocked.h) - a workgroup of BB_THREADS per block, 16 columns per pass in the s_y LDS slice,
 // the diagonal block of 64 rows on wave 0 (lane k: column k), the off-diagonal blocks on the fp64 16 x 16 x 4 MFMA.
-//   trsm TRANS is the first loop of bb_solve_block, NOTRANS its second one, statement for statement.
+//   trsm TRANS is bb_forward_sweep, NOTRANS bb_backward_sweep (batched_blocked.h): the two calls bb_solve_block itself makes.
 //   trmm NOTRANS, diagonal blocks ascending: Y1 = R11 X1 by the steps above, then Y1 += R12 X2 on the MFMA with K ascending over the columns to
 //     the right - rows that are not yet overwritten.  TRANS, descending: Y1 = R11^T X1, then Y1 += R01^T X0 with K ascending over the rows above.
 //     A row's sum is: its diagonal block's terms in the order above, then the MFMA terms in ascending K, four per instruction.
@@ -30,11 +30,12 @@
 // stored column alone.
 //
 // THE BIT CONTRACTS.  1. trsm(TRANS) followed by trsm(NOTRANS) leaves what cap_dpotrs_batched_blocked leaves: the same steps in the same order
-// on the same values (a store and a load between the halves change no bit), NaN for failed blocks included.  2. On a plan every block gets the
-// bits of the fixed-size entry on it alone: above 64 rows the same body on another address; up to 64 rows the group's own n is the n of every
+// on the same values (above 64 rows the same two functions; a store and a load between the halves change no bit), NaN for failed blocks
+// included.  2. On a plan every block gets the bits of the fixed-size entry on it alone: above 64 rows the same body on another address; up to 64 rows the group's own n is the n of every
 // step (a lane mask: each lane executes its block's fixed-size sequence), the wave-uniform skip is on the wave's largest n.  3. A column's
 // result and sumsq do not depend on the columns that travel with it.
-#include <algorithm>
+// SHARED (vbatch_plan.h): the argument rules, the grid and the dispatch of the entry points, the walk over a plan's classes and the lane
+// group's block lookup of tri_vbatched_kernel.
 #include <utility>
 #include <vector>
 
@@ -170,28 +171,13 @@ __global__ __launch_bounds__(64) void tri_vbatched_kernel(TbArgs g) {
   using Img = PbImg<NP>;
   __shared__ double s_img[G * Img::SIZE];
   const int lane = threadIdx.x, grp = lane / NP, k = lane % NP;
-  const int64_t at = (int64_t)blockIdx.x * G + grp;
-  int64_t blk = 0, off = 0, ld = 1, row = 0;
-  int n = 0;                                   // a dead group (the tail of a class): every predicate is false
-  if (at < g.count) {
-    blk = g.list[at];
-    const VbRec r = g.rec[blk];
-    off = r.off; ld = r.ld; row = r.row; n = (int)r.n;
-  }
-  int m = n;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const int t = __shfl_xor(m, o);
-    m = t > m ? t : m;
-  }
-  const int nmax = __builtin_amdgcn_readfirstlane(m);
+  const VbGroup v = vb_group<NP>(g.rec, g.list, g.count);
+  const int n = v.n, nmax = v.nmax;
   double* s = s_img + grp * Img::SIZE;
-#pragma unroll 8
-  for (int c = 0; c < nmax; c++)
-    if (k <= c && c < n) s[Img::at(k, c)] = g.R[off + k + (int64_t)c * ld];
-  const bool bad = g.info && n > 0 && g.info[blk] != 0;
+  vb_load_upper<Img>(g.R + v.off, v.ld, n, nmax, k, s);
+  const bool bad = g.info && n > 0 && g.info[v.blk] != 0;
   __syncthreads();
-  tb_small_passes<NP, OP>(s, g.B + row, g.ldb, g.nrhs, k, n > 0, n, nmax, bad, g.sumsq && n > 0 ? g.sumsq + blk * g.ldq : nullptr);
+  tb_small_passes<NP, OP>(s, g.B + v.row, g.ldb, g.nrhs, k, n > 0, n, nmax, bad, g.sumsq && n > 0 ? g.sumsq + v.blk * g.ldq : nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ 64 < n <= 256: a workgroup per block
@@ -227,79 +213,9 @@ __device__ __forceinline__ void tb_blocked_block(const double* R, const int64_t 
       for (int i = lane; i < npad; i += 64) s_y[i * BB_LDY + k] = (k < kc && i < n) ? B[i + (p0 + k) * ldb] : 0.0;
 
     if constexpr (OP == TB_SOLVE_T) {
-      // R^T y = b over the diagonal blocks in ascending order: the first loop of bb_solve_block
-      for (int d = 0; d < nblk; d++) {
-        const int k0 = d * BB_NB, nb = n - k0 < BB_NB ? n - k0 : BB_NB, t0 = k0 + BB_NB;
-        __syncthreads();
-        bb_load_upper(R + k0 + (int64_t)k0 * ldr, ldr, nb, lane, wave, BB_WAVES, s_img);
-        __syncthreads();
-        if (wave == 0) {
-          double x[BB_NB];
-#pragma unroll
-          for (int i = 0; i < BB_NB; i++) x[i] = i < nb ? s_y[(k0 + i) * BB_LDY + lr] : 0.0;
-          bb_forward_steps(x, s_img + bb_opaque_zero(), nb, std::make_integer_sequence<int, BB_NB>{});
-#pragma unroll
-          for (int i = 0; i < BB_NB; i++)
-            if (i < nb && lane < BB_KP) s_y[(k0 + i) * BB_LDY + lr] = x[i];
-        }
-        __syncthreads();
-        // B2 -= R12^T Y1: MFMA A operand lane -> R[k0 + kk + kg][t0 + bi 16 + lr] (negated), B operand Y[k0 + kk + kg][lr]; D: row kg + 4 r, column lr
-        const int mt = t0 < n ? (n - t0 + 15) >> 4 : 0;
-        for (int bi = wave; bi < mt; bi += BB_WAVES) {
-          const int i0 = t0 + bi * 16;
-          const bool ain = i0 + lr < n;
-          const double* ra = R + (k0 + kg) + (int64_t)(i0 + lr) * ldr;
-          double* y = s_y + (i0 + kg) * BB_LDY + lr;
-          const double* yb = s_y + (k0 + kg) * BB_LDY + lr;
-          d4 acc;
-#pragma unroll
-          for (int r = 0; r < 4; r++) acc[r] = y[4 * r * BB_LDY];
-#pragma unroll
-          for (int kk = 0; kk < BB_NB; kk += 4) {
-            double a = 0.0;
-            if (ain) a = -ra[kk];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, yb[kk * BB_LDY], acc, 0, 0, 0);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; r++)
-            if (i0 + kg + 4 * r < n) y[4 * r * BB_LDY] = acc[r];      // rows at or beyond n stay zero
-        }
-      }
+      bb_forward_sweep(R, ldr, n, s_img, s_y, lane, wave);
     } else if constexpr (OP == TB_SOLVE_N) {
-      // R x = y over the diagonal blocks in descending order: the second loop of bb_solve_block
-      for (int d = nblk - 1; d >= 0; d--) {
-        const int k0 = d * BB_NB, nb = n - k0 < BB_NB ? n - k0 : BB_NB;
-        __syncthreads();
-        bb_load_upper(R + k0 + (int64_t)k0 * ldr, ldr, nb, lane, wave, BB_WAVES, s_img);
-        __syncthreads();
-        if (wave == 0) {
-          double x[BB_NB];
-#pragma unroll
-          for (int i = 0; i < BB_NB; i++) x[i] = i < nb ? s_y[(k0 + i) * BB_LDY + lr] : 0.0;
-          bb_backward_steps(x, s_img + bb_opaque_zero(), nb, std::make_integer_sequence<int, BB_NB>{});
-#pragma unroll
-          for (int i = 0; i < BB_NB; i++)
-            if (i < nb && lane < BB_KP) s_y[(k0 + i) * BB_LDY + lr] = x[i];
-        }
-        __syncthreads();
-        // B1 -= R12 X2: MFMA A operand lane -> R[bi 16 + lr][k0 + kk + kg] (negated; zero at or beyond column n), B operand X[k0 + kk + kg][lr]
-        const int kend = (nb + 3) & ~3;
-        for (int bi = wave; bi < k0 / 16; bi += BB_WAVES) {
-          const double* ra = R + (bi * 16 + lr) + (int64_t)(k0 + kg) * ldr;
-          double* y = s_y + (bi * 16 + kg) * BB_LDY + lr;
-          const double* yb = s_y + (k0 + kg) * BB_LDY + lr;
-          d4 acc;
-#pragma unroll
-          for (int r = 0; r < 4; r++) acc[r] = y[4 * r * BB_LDY];
-          for (int kk = 0; kk < kend; kk += 4) {
-            double a = 0.0;
-            if (k0 + kk + kg < n) a = -ra[(int64_t)kk * ldr];
-            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a, yb[kk * BB_LDY], acc, 0, 0, 0);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; r++) y[4 * r * BB_LDY] = acc[r];
-        }
-      }
+      bb_backward_sweep(R, ldr, n, s_img, s_y, lane, wave);
     } else {
       // products: NOTRANS ascending (Y1 = R11 X1, += R12 X2 from the rows below, not yet overwritten), TRANS descending (Y1 = R11^T X1,
       // += R01^T X0 from the rows above)
@@ -395,38 +311,22 @@ __global__ __launch_bounds__(BB_THREADS) void tri_vbatched_blocked_kernel(TbArgs
 }
 
 // ------------------------------------------------------------------------------------------------ host
-template <int N> using tb_int = std::integral_constant<int, N>;
+constexpr int tb_op(int mul, int trans) { return mul ? (trans == CAP_TRANS ? TB_MUL_T : TB_MUL_N) : (trans == CAP_TRANS ? TB_SOLVE_T : TB_SOLVE_N); }
 
+// f(OP) with the operation as a template argument
 template <class F>
-void tb_with_op(int op, F f) {
-  if (op == TB_SOLVE_T) f(tb_int<TB_SOLVE_T>{});
-  else if (op == TB_SOLVE_N) f(tb_int<TB_SOLVE_N>{});
-  else if (op == TB_MUL_T) f(tb_int<TB_MUL_T>{});
-  else f(tb_int<TB_MUL_N>{});
-}
-template <class F>
-void tb_with_np(int np, F f) {
-  if (np == 8) f(tb_int<8>{});
-  else if (np == 16) f(tb_int<16>{});
-  else if (np == 32) f(tb_int<32>{});
-  else f(tb_int<64>{});
-}
-
-int tb_padded(int64_t n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
-int64_t tb_mul_clip(int64_t a, int64_t b) { return (int64_t)std::min<__int128>((__int128)a * b, INT64_MAX); }
+void tb_with_op(int op, F f) { vb_with_int<TB_SOLVE_T, TB_SOLVE_N, TB_MUL_T, TB_MUL_N>(op, f); }
 
 int tb_fixed(int mul, int uplo, int trans, int64_t n, int64_t nrhs, const double* R, int64_t ldr, int64_t stride_r, double* B, int64_t ldb,
              int64_t stride_b, int64_t batch, const int* info, double* sumsq, int64_t ldq, hipStream_t s) {
   if ((trans != CAP_NOTRANS && trans != CAP_TRANS) || n < 0 || nrhs < 0 || batch < 0) return CAP_ERR_ARG;
   if (n > 0 && nrhs > 0 && batch > 0 && (!R || !B)) return CAP_ERR_ARG;
-  if (ldr < n || ldb < n) return CAP_ERR_ARG;
-  if (batch > 1 && (stride_r < tb_mul_clip(ldr, n) || stride_b < tb_mul_clip(ldb, nrhs))) return CAP_ERR_ARG;
+  if (!vb_operand_ok(n, n, ldr, stride_r, batch) || !vb_operand_ok(n, nrhs, ldb, stride_b, batch)) return CAP_ERR_ARG;
   if (sumsq && ldq < nrhs) return CAP_ERR_ARG;
   if (uplo != CAP_UPPER) return CAP_ERR_UNSUPPORTED;    // as cap_dpotrs_batched
   if (n > TB_MAX) return CAP_ERR_UNSUPPORTED;
-  const int np = tb_padded(n);
-  const int64_t nwg = n <= BB_SMALL ? cap_ceil_div(batch, 64 / np) : batch;
-  if (nwg > 0x7fffffffLL) return CAP_ERR_UNSUPPORTED;      // one 1-D grid
+  const int64_t nwg = vb_grid(batch, vb_per_group(vb_class(n)));
+  if (nwg < 0) return CAP_ERR_UNSUPPORTED;
   if (n == 0 || nrhs == 0 || batch == 0) return CAP_OK;
   if (cap_acc_on()) {
     for (int64_t i = 0; i < batch; i++) {
@@ -439,13 +339,12 @@ int tb_fixed(int mul, int uplo, int trans, int64_t n, int64_t nrhs, const double
   TbArgs g = {};
   g.R = R; g.ldr = ldr; g.stride_r = stride_r; g.B = B; g.ldb = ldb; g.stride_b = stride_b; g.batch = batch; g.nrhs = nrhs; g.info = info;
   g.sumsq = sumsq; g.ldq = ldq; g.n = (int)n;
-  const int op = mul ? (trans == CAP_TRANS ? TB_MUL_T : TB_MUL_N) : (trans == CAP_TRANS ? TB_SOLVE_T : TB_SOLVE_N);
   const dim3 grid((unsigned)nwg);
-  tb_with_op(op, [&](auto OP) {
+  tb_with_op(tb_op(mul, trans), [&](auto OP) {
     if (n <= BB_SMALL) {
-      tb_with_np(np, [&](auto NP) { hipLaunchKernelGGL((tri_batched_kernel<decltype(NP)::value, decltype(OP)::value>), grid, dim3(64), 0, s, g); });
+      vb_with_int<8, 16, 32, 64>(vb_padded(n), [&](auto NP) { hipLaunchKernelGGL((tri_batched_kernel<NP(), OP()>), grid, dim3(64), 0, s, g); });
     } else {
-      hipLaunchKernelGGL((tri_batched_blocked_kernel<decltype(OP)::value>), grid, dim3(BB_THREADS), 0, s, g);
+      hipLaunchKernelGGL((tri_batched_blocked_kernel<OP()>), grid, dim3(BB_THREADS), 0, s, g);
     }
   });
   CAP_HIP(hipGetLastError());
@@ -463,16 +362,11 @@ int tb_plan(int mul, const cap_vbatch_plan* p, int uplo, int trans, int64_t nrhs
   if (p->device < 0) return CAP_ERR_HIP;
   TbArgs g = {};
   g.R = R; g.B = B; g.ldb = ldb; g.nrhs = nrhs; g.info = info; g.sumsq = sumsq; g.ldq = ldq; g.rec = p->d_rec;
-  const int op = mul ? (trans == CAP_TRANS ? TB_MUL_T : TB_MUL_N) : (trans == CAP_TRANS ? TB_SOLVE_T : TB_SOLVE_N);
-  for (int cls = 0; cls < VB_CLASSES; cls++) {
-    const std::vector<int64_t>& l = p->list[cls];
-    if (l.empty()) continue;
-    g.list = p->d_list + p->list_at[cls];
-    g.count = (int64_t)l.size();
+  return vb_for_each_class(p, [&](int cls, const int64_t* list, int64_t count, const std::vector<int64_t>& blocks, dim3 grid) {
+    g.list = list;
+    g.count = count;
     if (cap_acc_on()) {
-      cap_acc_r(p->d_rec, 0, p->batch * (int64_t)(sizeof(VbRec) / 8), 1);
-      cap_acc_r(g.list, 0, g.count, 1);
-      for (int64_t b : l) {
+      for (int64_t b : blocks) {
         const VbRec& r = p->rec[(size_t)b];
         cap_acc_r(R + r.off, r.ld, r.n, r.n, 1);
         cap_acc_rw(B + r.row, ldb, r.n, nrhs);
@@ -480,17 +374,14 @@ int tb_plan(int mul, const cap_vbatch_plan* p, int uplo, int trans, int64_t nrhs
         if (sumsq) cap_acc_w(sumsq + b * ldq, 0, nrhs, 1);
       }
     }
-    const dim3 grid((unsigned)cap_ceil_div(g.count, vb_per_group(cls)));
-    tb_with_op(op, [&](auto OP) {
+    tb_with_op(tb_op(mul, trans), [&](auto OP) {
       if (cls < 4) {
-        tb_with_np(8 << cls, [&](auto NP) { hipLaunchKernelGGL((tri_vbatched_kernel<decltype(NP)::value, decltype(OP)::value>), grid, dim3(64), 0, s, g); });
+        vb_with_int<8, 16, 32, 64>(8 << cls, [&](auto NP) { hipLaunchKernelGGL((tri_vbatched_kernel<NP(), OP()>), grid, dim3(64), 0, s, g); });
       } else {
-        hipLaunchKernelGGL((tri_vbatched_blocked_kernel<decltype(OP)::value>), grid, dim3(BB_THREADS), 0, s, g);
+        hipLaunchKernelGGL((tri_vbatched_blocked_kernel<OP()>), grid, dim3(BB_THREADS), 0, s, g);
       }
     });
-    CAP_HIP(hipGetLastError());
-  }
-  return CAP_OK;
+  });
 }
 
 }  // namespace

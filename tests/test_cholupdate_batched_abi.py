@@ -62,6 +62,7 @@ def test_fixed_size_arguments_are_checked_first(L):
     assert call(stride_r=n * n - 1) == ARG and call(stride_v=n * 3 - 1) == ARG
     assert call(ldr=n + 2, stride_r=(n + 2) * n - 1) == ARG and call(ldv=n + 2, stride_v=(n + 2) * 3 - 1) == ARG
     assert call(stride_r=-1) == ARG and call(stride_v=-1) == ARG
+    assert call(n=16, ldr=1 << 60, stride_r=0, ldv=16, stride_v=48, batch=2) == ARG          # ld * n = 2^64 does not wrap to 0
     assert call(stride_r=0, stride_v=0, batch=1, uplo=LOWER) == UNSUPPORTED       # one block needs no stride ...
     assert call(stride_r=0, batch=2, uplo=LOWER) == ARG and call(stride_v=0, batch=2, uplo=LOWER) == ARG   # ... two do
     assert call(R=None, uplo=LOWER) == ARG and call(ldv=n - 1, uplo=LOWER) == ARG

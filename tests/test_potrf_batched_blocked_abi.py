@@ -110,6 +110,15 @@ def test_single_block_needs_no_stride(L):
     assert L.cap_dpotrf_batched_blocked(LOWER, n, A, n, 0, 2, None, None, None) == ARG              # ... which two blocks do not
 
 
+def test_the_stride_rule_does_not_wrap(L):
+    """ld * columns beyond int64 (2^60 * 16 = 2^64 wraps to 0): the stride rule compares with the clipped product, so two blocks at stride 0
+    are refused like any other overlap - decided before any device work"""
+    big = 1 << 60
+    assert L.cap_dpotrf_batched_blocked(UPPER, 16, A, big, 0, 2, None, None, None) == ARG
+    assert L.cap_dpotrs_batched_blocked(UPPER, 16, 16, A, big, 0, B, 16, 16 * 16, 2, None, None) == ARG
+    assert L.cap_dpotrs_batched_blocked(UPPER, 16, 16, A, 16, 16 * 16, B, big, 0, 2, None, None) == ARG
+
+
 def test_the_existing_entries_keep_their_limit(L):
     assert L.cap_dpotrf_batched(UPPER, 65, A, 65, 65 * 65, 5, INFO, LOGDET, None) == UNSUPPORTED
     assert L.cap_dpotrs_batched(UPPER, 65, 3, A, 65, 65 * 65, B, 65, 65 * 3, 5, INFO, None) == UNSUPPORTED

@@ -102,6 +102,14 @@ def test_single_block_needs_no_stride(L):
     assert L.cap_dpotri_batched(LOWER, n, A, n, 0, 2, None, 0, None) == ARG
 
 
+def test_the_stride_rule_does_not_wrap(L):
+    """ld * columns beyond int64 (2^60 * 16 = 2^64 wraps to 0): the stride rule compares with the clipped product, so two blocks at stride 0
+    are refused like any other overlap - decided before any device work"""
+    big = 1 << 60
+    assert L.cap_dtrtri_batched(UPPER, 16, A, big, 0, 2, None, None) == ARG
+    assert L.cap_dpotri_batched(UPPER, 16, A, big, 0, 2, None, 0, None) == ARG
+
+
 def test_python_layer_names():
     from capital_amd import _lib, batched, lapack
     pt = lapack.ArgPack_trtri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)

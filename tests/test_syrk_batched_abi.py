@@ -76,6 +76,7 @@ def test_fixed_size_arguments_are_checked_in_the_documented_order(L):
     assert call(stride_c=0, stride_v=0, batch=1, uplo=LOWER) == UNSUPPORTED       # one block needs no stride ...
     assert call(stride_c=0, batch=2, uplo=LOWER) == ARG and call(stride_v=0, batch=2, uplo=LOWER) == ARG   # ... two do
     assert call(ldc=1 << 40, stride_c=1 << 62, n=1 << 30, ldv=1 << 30, stride_v=1 << 62) == ARG            # the clipped product
+    assert call(n=16, ldc=1 << 60, stride_c=0, ldv=16, stride_v=48, batch=2) == ARG                        # 2^64 does not wrap to 0
     assert call(**dict(big, ldc=256)) == ARG and call(**dict(big, ldv=256)) == ARG          # the argument rules come before the size limit
     # 8. LOWER, 9. n > 256, 10. the grid
     assert call(uplo=LOWER) == UNSUPPORTED and call(uplo=7) == UNSUPPORTED

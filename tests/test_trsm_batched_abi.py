@@ -68,6 +68,7 @@ def test_fixed_size_arguments_are_checked_in_the_documented_order(L, mul):
     assert call(stride_r=n * n - 1) == ARG and call(stride_b=n * 3 - 1) == ARG
     assert call(ldr=n + 2, stride_r=(n + 2) * n - 1) == ARG and call(ldb=n + 2, stride_b=(n + 2) * 3 - 1) == ARG
     assert call(stride_r=-1) == ARG and call(stride_b=-1) == ARG
+    assert call(n=16, ldr=1 << 60, stride_r=0, ldb=16, batch=2) == ARG and call(n=16, nrhs=16, ldr=16, ldb=1 << 60, stride_b=0, batch=2) == ARG   # 2^64 does not wrap to 0
     assert call(stride_r=0, stride_b=0, batch=1, uplo=LOWER) == UNSUPPORTED       # one block needs no stride ...
     assert call(stride_r=0, batch=2, uplo=LOWER) == ARG and call(stride_b=0, batch=2, uplo=LOWER) == ARG   # ... two do
     assert call(**dict(big, ldr=256)) == ARG and call(**dict(big, ldb=256)) == ARG          # the argument rules come before the size limit
