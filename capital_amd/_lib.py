@@ -52,6 +52,18 @@ SIGNATURES = {
     "cap_dtrmm_vbatched": (cint, [ptr, cint, cint, i64, ptr, ptr, i64, ptr, ptr]),
     "cap_dsyrk_batched": (cint, [cint, cint, i64, i64, dbl, ptr, i64, i64, dbl, ptr, i64, i64, ptr, cint, i64, ptr]),
     "cap_dsyrk_vbatched": (cint, [ptr, cint, cint, i64, dbl, ptr, i64, dbl, ptr, ptr, cint, ptr]),
+    "cap_dsymm_batched": (cint, [cint, cint, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, i64, ptr]),
+    "cap_dsymm_vbatched": (cint, [ptr, cint, cint, i64, dbl, ptr, ptr, i64, dbl, ptr, i64, ptr, i64, ptr]),
+    "cap_dlansy_batched": (cint, [cint, cint, i64, ptr, i64, i64, i64, ptr, ptr]),
+    "cap_dlansy_vbatched": (cint, [ptr, cint, cint, ptr, ptr, ptr]),
+    "cap_dpocon_batched_work_size": (i64, [i64, i64]),
+    "cap_dpocon_vbatched_work_size": (i64, [ptr]),
+    "cap_dpocon_batched": (cint, [cint, i64, ptr, i64, i64, i64, ptr, ptr, ptr, ptr, ptr]),
+    "cap_dpocon_vbatched": (cint, [ptr, cint, ptr, ptr, ptr, ptr, ptr, ptr]),
+    "cap_dpoerr_batched_work_size": (i64, [i64, i64, i64]),
+    "cap_dpoerr_vbatched_work_size": (i64, [ptr, i64]),
+    "cap_dpoerr_batched": (cint, [cint, i64, i64, ptr, i64, i64, ptr, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr, ptr, i64, ptr, ptr]),
+    "cap_dpoerr_vbatched": (cint, [ptr, cint, i64, ptr, ptr, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, ptr, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

@@ -13,6 +13,10 @@ trsm / trmm / mahalanobis (and the VarBatch forms): ONE half of the factor appli
 Mahalanobis distances, one launch (cap_dtrsm_batched / cap_dtrmm_batched / cap_dtrsm_vbatched / cap_dtrmm_vbatched, csrc/trsm_batched.hip).
 syrk / schur (and VarBatch.syrk): FORMING the blocks - alpha V^T V + beta C (+ shift I) into the triangle potrf reads, and the Schur
 complement C - B A^-1 B^T from a factor, one launch per product (cap_dsyrk_batched / cap_dsyrk_vbatched, csrc/syrk_batched.hip).
+symm / norm1 / rcond / error_bounds (and the VarBatch forms): how many digits of those answers mean anything - the product with the symmetric
+block itself from the triangle potrf reads, its 1-norm, the EXACT reciprocal condition number and the forward / backward error bounds of
+a solve, from the computed inverse (cap_dsymm_batched / cap_dlansy_batched / cap_dpocon_batched / cap_dpoerr_batched and their _vbatched
+forms, csrc/symm_batched.hip).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
@@ -33,6 +37,12 @@ _PACK_TS = lapack.ArgPack_trsm_batched(lapack.Order.AlapackColumnMajor, lapack.U
 _PACK_TM = lapack.ArgPack_trmm_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_VTS = lapack.ArgPack_trsm_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_VTM = lapack.ArgPack_trmm_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_N = lapack.ArgPack_lansy_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper, '1')
+_PACK_C = lapack.ArgPack_pocon_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_E = lapack.ArgPack_poerr_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VN = lapack.ArgPack_lansy_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper, '1')
+_PACK_VC = lapack.ArgPack_pocon_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VE = lapack.ArgPack_poerr_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 
 
 def _check(t, name, dims):
@@ -61,10 +71,11 @@ def _blocks(A, name):
 _COUNT = {"right-hand side": "nrhs", "column": "k"}     # what the docstrings call the number of columns of each kind
 
 
-def _columns(R, X, name, noun):
+def _columns(R, X, name, noun, first="R"):
     """(batch, n, ldr, stride_r, X3, count, ldx, stride_x) of the factors R and of X - potrs's and trsm's B (noun "right-hand side") or
-    update's V ("column"): (batch, count, n) or (batch, n), every column contiguous, no two overlapping, on R's device"""
-    batch, n, ldr, stride_r = _blocks(R, "R")
+    update's V ("column"): (batch, count, n) or (batch, n), every column contiguous, no two overlapping, on R's device; first: what the
+    messages call the block operand"""
+    batch, n, ldr, stride_r = _blocks(R, first)
     _check(X, name, (2, 3))
     X3 = X.unsqueeze(1) if X.dim() == 2 else X
     if X3.shape[0] != batch or X3.shape[2] != n:
@@ -78,7 +89,7 @@ def _columns(R, X, name, noun):
     if ldx < n or (batch > 1 and stride_x < ldx * count):
         raise _lib.CapitalError("%s: %ss overlap (strides %s)" % (name, noun, X.stride()))
     if X.device != R.device:
-        raise _lib.CapitalError("R and %s live on different devices" % name)
+        raise _lib.CapitalError("%s and %s live on different devices" % (first, name))
     return batch, n, ldr, stride_r, X3, count, ldx, max(stride_x, 0)
 
 
@@ -296,6 +307,108 @@ def schur(R, B, C, info=None):
     return syrk(B, C, trans=True, alpha=-1.0, beta=1.0)
 
 
+def _symm_pack(alpha, beta, absolute):
+    return blas.ArgPack_symm(blas.Order.AblasColumnMajor, blas.UpLo.AblasUpper, alpha, beta, absolute)
+
+
+def _same_columns(ref, got, name):
+    """the (batch, n, X3, nrhs, ldx, stride_x) part of _columns for a second operand, which must match the first in shape"""
+    if got[0] != ref[0] or got[1] != ref[1] or got[5] != ref[5]:
+        raise _lib.CapitalError("%s must have the shape of X" % name)
+    return got[4], got[6], got[7]
+
+
+def _vector(t, batch, name, ref):
+    """a contiguous (batch,) fp64 device tensor on ref's device"""
+    _check(t, name, (1,))
+    if t.shape[0] != batch or not t.is_contiguous():
+        raise _lib.CapitalError("%s must be a contiguous (batch,) tensor with batch = %d, got shape %s" % (name, batch, tuple(t.shape)))
+    if t.device != ref.device:
+        raise _lib.CapitalError("%s lives on another device" % name)
+    return t
+
+
+def symm(A, X, B=None, alpha=1.0, beta=0.0, absolute=False, out=None):
+    """The product with the symmetric blocks themselves, one launch: out[i] <- beta B[i] + alpha A_i X[i] (per right-hand side: a block-diagonal
+    matvec, residuals b - A x with alpha=-1, beta=1).  A: fp64 device tensor of shape (batch, n, n), n <= 256, under potrf's layout rules;
+    only the triangle potrf reads is read - the upper triangle of the column-major block, which is the LOWER triangle of A[i] in torch's
+    row-major reading - and the other one is never touched, so A may be what syrk or potri wrote.  It is the matrix itself, not its factor.
+    X, B, out: (batch, nrhs, n) or (batch, n) with stride(-1) == 1, as potrs's B.  B=None needs beta == 0; beta == 0 does not read B (NaN
+    there does not propagate).  out=None: a fresh tensor of X's shape; out may be B (in place), it must not overlap A or X.
+    absolute=True takes |.| of every element of A, X and B on load (|A||x| + |b|).  The summation order is fixed
+    (csrc/symm_batched.hip): the same bits for any batch, layout or set of columns that travel together.  Returns out.  Asynchronous on
+    the current stream."""
+    cx = _columns(A, X, "X", "right-hand side", first="A")
+    batch, n, lda, stride_a, X3, nrhs, ldx, stride_x = cx
+    if B is None:
+        if beta != 0:
+            raise _lib.CapitalError("B=None needs beta == 0")
+        B3, ldb, stride_b = None, max(n, 1), 0
+    else:
+        B3, ldb, stride_b = _same_columns(cx, _columns(A, B, "B", "right-hand side", first="A"), "B")
+    if out is None:
+        out = torch.zeros_like(X, memory_format=torch.contiguous_format)
+    Y3, ldy, stride_y = _same_columns(cx, _columns(A, out, "out", "right-hand side", first="A"), "out")
+    if out.dim() != X.dim():
+        raise _lib.CapitalError("out must have the shape of X")
+    for t, name in ((A, "A"), (X, "X")):
+        (a0, a1), (b0, b1) = _span(t), _span(out)
+        if alpha != 0 and a0 < b1 and b0 < a1:
+            raise _lib.CapitalError("%s and out overlap" % name)
+    blas.engine._symm_batched(A, X3, B3, Y3, n, nrhs, lda, stride_a, ldx, stride_x, ldb, stride_b, ldy, stride_y, batch,
+                              _symm_pack(alpha, beta, absolute))
+    return out
+
+
+def norm1(A):
+    """The 1-norms |A_i|_1 = max_j sum_i |a_ij| of the symmetric blocks (equal to their infinity norms), one launch.  A as in symm: only
+    the triangle potrf reads is read (the LOWER triangle of A[i] in torch's reading) - and it must hold the matrix BEFORE potrf overwrote
+    it: take the norms first, or keep a copy.  Returns a fresh fp64 tensor of shape (batch,); a NaN in a block's triangle gives NaN.
+    Asynchronous on the current stream."""
+    batch, n, lda, stride = _blocks(A, "A")
+    out = torch.zeros(max(batch, 1), dtype=torch.float64, device=A.device)
+    lapack.engine._lansy_batched(A, n, lda, stride, batch, out, _PACK_N)
+    return out[:batch]
+
+
+def rcond(R, anorm, info=None):
+    """EXACT reciprocal condition numbers 1 / (|A_i|_1 |A_i^-1|_1) from the factors potrf left in R (same layout rules as potrf's A,
+    n <= 256; R is not written): the inverse of every block is computed into a work tensor (potri on a copy of the triangle potrf wrote,
+    the LOWER one in torch's reading) and its 1-norm taken - four launches, whatever the batch; not LAPACK's estimate, which for blocks
+    this small costs more and answers less.  anorm: what norm1 returned for the matrices before potrf, a (batch,) fp64 device tensor.
+    info: what potrf returned, or None - a block with info != 0 gets NaN.  anorm == 0 gives 0, NaN gives NaN; for n == 0 the result is 0.
+    Returns a fresh fp64 tensor of shape (batch,).  Asynchronous on the current stream; nothing is read back."""
+    batch, n, ldr, stride_r = _blocks(R, "R")
+    anorm = _vector(anorm, batch, "anorm", R)
+    out = torch.zeros(max(batch, 1), dtype=torch.float64, device=R.device)
+    lapack.engine._pocon_batched(R, n, ldr, stride_r, batch, anorm if batch > 0 else None, _info(info, R), out, _PACK_C)
+    return out[:batch]
+
+
+def error_bounds(A, R, B, X, info=None, ferr=True):
+    """Error bounds of the solutions X of A_i x = b that potrs computed, as LAPACK's dporfs reports them: returns (ferr, berr), fresh fp64
+    tensors of shape (batch, nrhs) - (batch,) for 2-D right-hand sides.  berr: the componentwise backward error max_r |b - A x|_r /
+    (|A||x| + |b|)_r.  ferr: a bound on |x - x_true|_inf / |x|_inf, | |A^-1| (|r| + (n + 1) eps (|A||x| + |b|)) |_inf / |x|_inf with the
+    COMPUTED inverse (potri on a copy of R) in place of an estimate of that norm.  A: the matrices BEFORE potrf overwrote them (keep a
+    copy), R: the factors; of both only the triangle potrf reads is read (the LOWER one in torch's reading).  B, X: (batch, nrhs, n) or
+    (batch, n) with stride(-1) == 1, the right-hand sides and the solutions.  Nothing but the results is written.  info: what potrf
+    returned, or None - a block with info != 0 gets NaN.  ferr=False skips the inverse (one launch instead of four) and returns
+    (None, berr).  Asynchronous on the current stream; nothing is read back."""
+    cx = _columns(R, X, "X", "right-hand side")
+    batch, n, ldr, stride_r, X3, nrhs, ldx, stride_x = cx
+    B3, ldb, stride_b = _same_columns(cx, _columns(R, B, "B", "right-hand side"), "B")
+    ab, an, lda, stride_a = _blocks(A, "A")
+    if ab != batch or an != n or A.device != R.device:
+        raise _lib.CapitalError("A must be (batch, n, n) like R and live on its device, got shape %s" % (tuple(A.shape),))
+    lde = max(nrhs, 1)
+    fe = torch.zeros((max(batch, 1), lde), dtype=torch.float64, device=R.device) if ferr else None
+    be = torch.zeros((max(batch, 1), lde), dtype=torch.float64, device=R.device)
+    lapack.engine._poerr_batched(A, R, B3, X3, n, nrhs, lda, stride_a, ldr, stride_r, ldb, stride_b, ldx, stride_x, batch, _info(info, R),
+                                 fe, be, lde, _PACK_E)
+    shape = lambda t: None if t is None else (t[:batch, 0] if X.dim() == 2 else t[:batch, :nrhs])
+    return shape(fe), shape(be)
+
+
 class VarBatch:
     """A batch of SPD blocks of DIFFERENT sizes 0 <= n_i <= 256 inside ONE flat fp64 device tensor: block i is the n_i x n_i column-major block
     at element offsets[i] with leading dimension ld[i].  sizes, ld, offsets: host sequences of ints; ld=None: ld[i] = max(n_i, 1);
@@ -398,10 +511,10 @@ class VarBatch:
         row at which that was found in info[i] and NaN from that row on.  Returns info.  Asynchronous on the current stream."""
         return self._cholupdate(R, V, info, -1)
 
-    def _stacked(self, R, X, name, noun):
+    def _stacked(self, R, X, name, noun, first="R"):
         """(X2, count, ldx) of the flat factors R and of the stacked X - potrs's and trsm's B (noun "right-hand side") or update's V
         ("column"): (rows,) or (count, rows), every column contiguous, no two overlapping, on R's device"""
-        self._flat(R, "R")
+        self._flat(R, first)
         _check(X, name, (1, 2))
         X2 = X.unsqueeze(0) if X.dim() == 1 else X
         if X2.shape[1] != self.rows:
@@ -413,7 +526,7 @@ class VarBatch:
         if ldx < self.rows:
             raise _lib.CapitalError("%s: %ss overlap (strides %s)" % (name, noun, X.stride()))
         if X.device != R.device:
-            raise _lib.CapitalError("R and %s live on different devices" % name)
+            raise _lib.CapitalError("%s and %s live on different devices" % (first, name))
         return X2, count, ldx
 
     def trsm(self, R, B, trans=True, info=None, sumsq=False):
@@ -480,6 +593,73 @@ class VarBatch:
         blas.engine._syrk_vbatched(self._plan, V2, C, k, ldv, self.batch, _syrk_pack(trans, alpha, beta), shift=_shift(shift, self.batch, C),
                                    fill=bool(symmetric))
         return C
+
+    def symm(self, A, X, B=None, alpha=1.0, beta=0.0, absolute=False, out=None):
+        """The product with every symmetric block itself, one launch per size class: block i of the stacked out <- beta b_i + alpha A_i x_i -
+        the block-diagonal matvec.  A: the flat tensor; of every block only the triangle potrf reads is read (the LOWER one in torch's
+        reading, .block).  X, B, out: (rows,) or (nrhs, rows) with stride(-1) == 1, as potrs's B.  B=None needs beta == 0; out=None: a fresh
+        tensor; out may be B, it must not overlap A or X.  absolute=True: |.| of every element on load.  Every block gets the bits of the
+        fixed-size symm on it alone.  Returns out.  Asynchronous on the current stream."""
+        X2, nrhs, ldx = self._stacked(A, X, "X", "right-hand side", first="A")
+        if B is None:
+            if beta != 0:
+                raise _lib.CapitalError("B=None needs beta == 0")
+            B2, ldb = None, max(self.rows, 1)
+        else:
+            B2, nb, ldb = self._stacked(A, B, "B", "right-hand side", first="A")
+            if nb != nrhs or B.dim() != X.dim():
+                raise _lib.CapitalError("B must have the shape of X")
+        if out is None:
+            out = torch.zeros_like(X, memory_format=torch.contiguous_format)
+        Y2, ny, ldy = self._stacked(A, out, "out", "right-hand side", first="A")
+        if ny != nrhs or out.dim() != X.dim():
+            raise _lib.CapitalError("out must have the shape of X")
+        for t, name in ((A, "A"), (X, "X")):
+            (a0, a1), (b0, b1) = _span(t), _span(out)
+            if alpha != 0 and a0 < b1 and b0 < a1:
+                raise _lib.CapitalError("%s and out overlap" % name)
+        blas.engine._symm_vbatched(self._plan, A, X2, B2, Y2, nrhs, ldx, ldb, ldy, _symm_pack(alpha, beta, absolute))
+        return out
+
+    def norm1(self, A):
+        """The 1-norms of all symmetric blocks of the flat tensor A, one launch per size class: a fresh fp64 tensor of batch entries in batch
+        order, 0 for an empty block.  Only the triangle potrf reads is read (the LOWER one in torch's reading, .block), and it must hold the
+        matrices BEFORE potrf overwrote them.  Asynchronous on the current stream."""
+        self._flat(A, "A")
+        out = torch.zeros(max(self.batch, 1), dtype=torch.float64, device=A.device)
+        lapack.engine._lansy_vbatched(self._plan, A, self.batch, out, _PACK_VN)
+        return out[:self.batch]
+
+    def rcond(self, R, anorm, info=None):
+        """EXACT reciprocal condition numbers of all blocks from the factors potrf left in the flat tensor R (not written; the triangle potrf
+        wrote is read - the LOWER one in torch's reading), as rcond of this module: three launches per size class plus one.  anorm: what
+        norm1 returned before potrf; info: what potrf returned, or None - a failed block gets NaN.  Returns a fresh fp64 tensor of batch
+        entries in batch order, 0 for an empty block.  Every block gets the bits of the fixed-size rcond on it alone.  Asynchronous on the
+        current stream."""
+        self._flat(R, "R")
+        anorm = _vector(anorm, self.batch, "anorm", R)
+        out = torch.zeros(max(self.batch, 1), dtype=torch.float64, device=R.device)
+        lapack.engine._pocon_vbatched(self._plan, R, self.batch, anorm if self.batch > 0 else None, _info(info, R), out, _PACK_VC)
+        return out[:self.batch]
+
+    def error_bounds(self, A, R, B, X, info=None, ferr=True):
+        """(ferr, berr) of the stacked solutions X of A_i x = b_i, as error_bounds of this module: fresh fp64 tensors of shape (batch, nrhs) -
+        (batch,) for 1-D right-hand sides - in batch order, 0 for an empty block.  A: the flat tensor of the matrices BEFORE potrf
+        overwrote them, R: their factors; of both the triangle potrf reads is read (the LOWER one in torch's reading, .block).  B, X:
+        (rows,) or (nrhs, rows) with stride(-1) == 1.  info: what potrf returned, or None - a failed block gets NaN.  ferr=False skips the
+        inverses and returns (None, berr).  Every block gets the bits of the fixed-size error_bounds on it alone.  Asynchronous on the
+        current stream."""
+        self._flat(A, "A")
+        X2, nrhs, ldx = self._stacked(R, X, "X", "right-hand side")
+        B2, nb, ldb = self._stacked(R, B, "B", "right-hand side")
+        if nb != nrhs or B.dim() != X.dim() or A.device != R.device:
+            raise _lib.CapitalError("B must have the shape of X, and A must live on R's device")
+        lde = max(nrhs, 1)
+        fe = torch.zeros((max(self.batch, 1), lde), dtype=torch.float64, device=R.device) if ferr else None
+        be = torch.zeros((max(self.batch, 1), lde), dtype=torch.float64, device=R.device)
+        lapack.engine._poerr_vbatched(self._plan, A, R, B2, X2, nrhs, ldb, ldx, self.batch, _info(info, R), fe, be, lde, _PACK_VE)
+        shape = lambda t: None if t is None else (t[:self.batch, 0] if X.dim() == 1 else t[:self.batch, :nrhs])
+        return shape(fe), shape(be)
 
     def block(self, A, i):
         """The n_i x n_i view of block i of the flat tensor A in torch's row-major reading: block(A, i)[r, c] is element (c, r) of the

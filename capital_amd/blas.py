@@ -40,6 +40,7 @@ class Method(enum.IntEnum):
     AblasGemm = 0x0
     AblasTrmm = 0x1
     AblasSyrk = 0x10
+    AblasSymm = 0x11            # extension: not in the reference's enum
 
 
 class ArgPack_gemm:
@@ -61,6 +62,13 @@ class ArgPack_syrk:
         self.method = Method.AblasSyrk
         self.order, self.uplo, self.transposeA = Order(order), UpLo(uplo), Transpose(transposeA)
         self.alpha, self.beta = float(alpha), float(beta)
+
+
+class ArgPack_symm:
+    def __init__(self, order, uplo, alpha, beta, absolute=False):
+        self.method = Method.AblasSymm
+        self.order, self.uplo = Order(order), UpLo(uplo)
+        self.alpha, self.beta, self.absolute = float(alpha), float(beta), bool(absolute)
 
 
 def _require_colmajor(order):
@@ -128,6 +136,31 @@ class engine:
         st = _lib.lib().cap_dsyrk_vbatched(plan, int(srcPackage.uplo), int(srcPackage.transposeA), k, srcPackage.alpha, dptr(matrixV), ldv,
                                            srcPackage.beta, dptr(matrixC), engine._shift_ptr(shift, batch), 1 if fill else 0, cur_stream(stream))
         _lib.check(st, "blas::engine::_syrk_vbatched")
+
+    @staticmethod
+    def _symm_batched(matrixA, matrixX, matrixB, matrixY, n, nrhs, lda, stride_a, ldx, stride_x, ldb, stride_b, ldy, stride_y, batch, srcPackage,
+                      stream=None):
+        """Y_i (n x nrhs, ld ldy, at matrixY + i stride_y) <- beta B_i + alpha A_i X_i with the SYMMETRIC n x n blocks A_i of which only the
+        upper triangle of the column-major block at matrixA + i stride_a (ld lda) is read, n <= 256, any nrhs, in one launch
+        (cap_dsymm_batched).  alpha, beta, uplo and absolute (|.| of every element of A, X and B on load) come from the ArgPack_symm.
+        beta == 0 does not read B (matrixB may be None); matrixY may be matrixB, it must not overlap A or X.  Asynchronous."""
+        _require_colmajor(srcPackage.order)
+        if n > 256:
+            raise _lib.CapitalError("_symm_batched takes blocks of at most 256 rows, got n = %d" % n)
+        st = _lib.lib().cap_dsymm_batched(int(srcPackage.uplo), 1 if srcPackage.absolute else 0, n, nrhs, srcPackage.alpha, dptr(matrixA), lda,
+                                          stride_a, dptr(matrixX), ldx, stride_x, srcPackage.beta, dptr(matrixB), ldb, stride_b, dptr(matrixY),
+                                          ldy, stride_y, batch, cur_stream(stream))
+        _lib.check(st, "blas::engine::_symm_batched")
+
+    @staticmethod
+    def _symm_vbatched(plan, matrixA, matrixX, matrixB, matrixY, nrhs, ldx, ldb, ldy, srcPackage, stream=None):
+        """The same for the blocks of a cap_vbatch_plan (n_i <= 256; a plan refuses larger blocks when it is made): matrixA is the flat tensor
+        of the plan, matrixX / matrixB / matrixY the stacked (sum n_i) x nrhs systems of _potrs_vbatched.  cap_dsymm_vbatched, one launch
+        per non-empty size class.  Asynchronous."""
+        _require_colmajor(srcPackage.order)
+        st = _lib.lib().cap_dsymm_vbatched(plan, int(srcPackage.uplo), 1 if srcPackage.absolute else 0, nrhs, srcPackage.alpha, dptr(matrixA),
+                                           dptr(matrixX), ldx, srcPackage.beta, dptr(matrixB), ldb, dptr(matrixY), ldy, cur_stream(stream))
+        _lib.check(st, "blas::engine::_symm_vbatched")
 
     @staticmethod
     def _trsm(matrixA, matrixB, m, n, lda, ldb, srcPackage, stream=None):

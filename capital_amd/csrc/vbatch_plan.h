@@ -1,9 +1,10 @@
 // What the batched fp64 family shares outside its arithmetic (the arithmetic: batched_small.h, batched_blocked.h, batched_inverse.h,
 // chud_step.h).  HOST: the size classes, the clipped product, the one-1-D-grid limit, the runtime-value-to-template-argument dispatch and the
-// operand rule of the fixed-size entry points - used by all seven translation units (potrf_batched.hip, potrf_batched_blocked.hip,
-// potri_batched.hip, potrf_vbatched.hip, cholupdate_batched.hip, trsm_batched.hip, syrk_batched.hip).  THE PLAN (cap_vbatch_plan, built by
-// potrf_vbatched.hip) as the four translation units that run on it see it - potrf_vbatched.hip (factor, solve, inverse),
-// cholupdate_batched.hip (update / downdate), trsm_batched.hip (solves and products), syrk_batched.hip (rank-k products) - with the walk over
+// operand rule of the fixed-size entry points - used by all eight translation units (potrf_batched.hip, potrf_batched_blocked.hip,
+// potri_batched.hip, potrf_vbatched.hip, cholupdate_batched.hip, trsm_batched.hip, syrk_batched.hip, symm_batched.hip).  THE PLAN
+// (cap_vbatch_plan, built by potrf_vbatched.hip) as the five translation units that run on it see it - potrf_vbatched.hip (factor, solve,
+// inverse), cholupdate_batched.hip (update / downdate), trsm_batched.hip (solves and products), syrk_batched.hip (rank-k products),
+// symm_batched.hip (symmetric products, norms, rcond, error bounds) - with the walk over
 // its classes (vb_for_each_class) and, DEVICE, a lane group's block lookup (vb_group, vb_wave_max, vb_load_upper).
 #pragma once
 #include <stdint.h>

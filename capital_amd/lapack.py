@@ -6,7 +6,8 @@ number from the factor, LAPACK's dpocon), _poerr (the error bounds of LAPACK's d
 _potri_batched (the factor, solve, triangular inverse and SPD inverse of many small blocks of one size in one launch) and _potrf_vbatched /
 _potrs_vbatched / _potri_vbatched (the same for blocks of different sizes, described by a cap_vbatch_plan) and _cholupdate_batched /
 _cholupdate_vbatched (the rank-k update / downdate of those factors) and _trsm_batched / _trmm_batched / _trsm_vbatched / _trmm_vbatched
-(one triangular solve or product with those factors) have no counterpart upstream.
+(one triangular solve or product with those factors) and _lansy_batched / _pocon_batched / _poerr_batched with their _vbatched forms (the
+1-norms, the exact reciprocal condition numbers and the solve error bounds of those blocks) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -59,6 +60,12 @@ class Method(enum.IntEnum):
     AlapackTrmmBatched = 0x15          # extension: not in the reference's enum
     AlapackTrsmVbatched = 0x16         # extension: not in the reference's enum
     AlapackTrmmVbatched = 0x17         # extension: not in the reference's enum
+    AlapackLansyBatched = 0x18         # extension: not in the reference's enum
+    AlapackPoconBatched = 0x19         # extension: not in the reference's enum
+    AlapackPoerrBatched = 0x1A         # extension: not in the reference's enum
+    AlapackLansyVbatched = 0x1B        # extension: not in the reference's enum
+    AlapackPoconVbatched = 0x1C        # extension: not in the reference's enum
+    AlapackPoerrVbatched = 0x1D        # extension: not in the reference's enum
 
 
 class ArgPack_potrf:
@@ -185,6 +192,42 @@ class ArgPack_trmm_vbatched:
     def __init__(self, order, uplo, diag=Diag.AlapackNonUnit):
         self.method = Method.AlapackTrmmVbatched
         self.order, self.uplo, self.diag = Order(order), UpLo(uplo), Diag(diag)
+
+
+class ArgPack_lansy_batched:
+    def __init__(self, order, uplo, norm='1'):
+        self.method = Method.AlapackLansyBatched
+        self.order, self.uplo, self.norm = Order(order), UpLo(uplo), norm
+
+
+class ArgPack_pocon_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPoconBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_poerr_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPoerrBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_lansy_vbatched:
+    def __init__(self, order, uplo, norm='1'):
+        self.method = Method.AlapackLansyVbatched
+        self.order, self.uplo, self.norm = Order(order), UpLo(uplo), norm
+
+
+class ArgPack_pocon_vbatched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPoconVbatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_poerr_vbatched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPoerrVbatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
 
 
 BATCHED_SMALL_MAX = 64      # cap_dpotrf_batched / cap_dpotrs_batched: a wavefront per block
@@ -509,6 +552,96 @@ class engine:
         st = L.cap_dtrmm_vbatched(plan, int(srcPackage.uplo), 1 if trans else 0, nrhs, dptr(matrixR), dptr(matrixB), ldb,
                                   engine._batched_info(info, batch), cur_stream(stream))
         _lib.check(st, "lapack::engine::_trmm_vbatched")
+
+    @staticmethod
+    def _colmajor(srcPackage):
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+
+    @staticmethod
+    def _out_ptr(t, count, name):
+        if t is None:
+            return None
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < count:
+            raise _lib.CapitalError("%s must be a contiguous fp64 device tensor of at least %d entries" % (name, count))
+        return t.data_ptr()
+
+    @staticmethod
+    def _lansy_batched(matrixA, n, lda, stride_a, batch, out, srcPackage, stream=None):
+        """out[i] <- the 1-norm (norm '1' / 'O' / 'I' of the ArgPack: one number for a symmetric matrix) of the symmetric n x n blocks
+        (n <= 256) whose upper triangles lie at matrixA + i stride_a (column-major, ld lda), in one launch (cap_dlansy_batched).  out: a
+        contiguous fp64 device tensor of batch entries.  A NaN in a triangle gives NaN.  Asynchronous."""
+        engine._colmajor(srcPackage)
+        _batched_blocked(None, n)
+        st = _lib.lib().cap_dlansy_batched(ord(str(srcPackage.norm)[0]), int(srcPackage.uplo), n, dptr(matrixA), lda, stride_a, batch,
+                                           engine._out_ptr(out, batch, "out"), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_lansy_batched")
+
+    @staticmethod
+    def _lansy_vbatched(plan, matrixA, batch, out, srcPackage, stream=None):
+        """The same for the blocks of a cap_vbatch_plan (n_i <= 256; a plan refuses larger blocks when it is made) inside the flat matrixA:
+        cap_dlansy_vbatched, one launch per non-empty size class; out in batch order, the entries of empty blocks are not written.
+        Asynchronous."""
+        engine._colmajor(srcPackage)
+        st = _lib.lib().cap_dlansy_vbatched(plan, ord(str(srcPackage.norm)[0]), int(srcPackage.uplo), dptr(matrixA),
+                                            engine._out_ptr(out, batch, "out"), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_lansy_vbatched")
+
+    @staticmethod
+    def _pocon_batched(matrixR, n, ldr, stride_r, batch, anorm, info, rcond, srcPackage, stream=None):
+        """rcond[i] <- 1 / (anorm[i] * |A_i^-1|_1) with the COMPUTED inverse of every block, from the factors _potrf_batched left at
+        matrixR + i stride_r (n <= 256; not written): cap_dpocon_batched, four launches whatever the batch.  anorm, rcond: contiguous fp64
+        device tensors of batch entries; info: what _potrf_batched returned, or None - a failed block gets NaN.  The work tensor is
+        allocated here.  Asynchronous."""
+        engine._colmajor(srcPackage)
+        _batched_blocked(None, n)
+        L = _lib.lib()
+        work = scratch(L.cap_dpocon_batched_work_size(n, batch), rcond)
+        st = L.cap_dpocon_batched(int(srcPackage.uplo), n, dptr(matrixR), ldr, stride_r, batch, engine._out_ptr(anorm, batch, "anorm"),
+                                  engine._batched_info(info, batch), engine._out_ptr(rcond, batch, "rcond"), dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_pocon_batched")
+
+    @staticmethod
+    def _pocon_vbatched(plan, matrixR, batch, anorm, info, rcond, srcPackage, stream=None):
+        """The same for the blocks of a cap_vbatch_plan (n_i <= 256; a plan refuses larger blocks when it is made): cap_dpocon_vbatched, three
+        launches per non-empty size class plus one; the entries of empty blocks are not written.  Asynchronous."""
+        engine._colmajor(srcPackage)
+        L = _lib.lib()
+        work = scratch(L.cap_dpocon_vbatched_work_size(plan), rcond)
+        st = L.cap_dpocon_vbatched(plan, int(srcPackage.uplo), dptr(matrixR), engine._out_ptr(anorm, batch, "anorm"),
+                                   engine._batched_info(info, batch), engine._out_ptr(rcond, batch, "rcond"), dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_pocon_vbatched")
+
+    @staticmethod
+    def _poerr_batched(matrixA, matrixR, matrixB, matrixX, n, nrhs, lda, stride_a, ldr, stride_r, ldb, stride_b, ldx, stride_x, batch, info,
+                       ferr, berr, lde, srcPackage, stream=None):
+        """The bounds of LAPACK's dporfs for the solutions X_i of A_i X = B_i, n <= 256: berr[i lde + j] the componentwise backward error,
+        ferr[i lde + j] the forward error bound | |A_i^-1| w_j |_inf / |x_j|_inf with the COMPUTED inverse (cap_dpoerr_batched; one launch
+        for berr alone, four with ferr).  matrixA: the blocks before the factorization (upper triangles), matrixR: their factors; nothing is
+        written but ferr / berr (contiguous fp64 device tensors of batch x lde entries, either may be None).  A block with info != 0 gets
+        NaN.  The work tensor is allocated here.  Asynchronous."""
+        engine._colmajor(srcPackage)
+        _batched_blocked(None, n)
+        L = _lib.lib()
+        work = scratch(L.cap_dpoerr_batched_work_size(n, nrhs, batch), matrixX) if ferr is not None else None
+        st = L.cap_dpoerr_batched(int(srcPackage.uplo), n, nrhs, dptr(matrixA), lda, stride_a, dptr(matrixR), ldr, stride_r, dptr(matrixB), ldb,
+                                  stride_b, dptr(matrixX), ldx, stride_x, batch, engine._batched_info(info, batch),
+                                  engine._out_ptr(ferr, batch * lde, "ferr"), engine._out_ptr(berr, batch * lde, "berr"), lde, dptr(work),
+                                  cur_stream(stream))
+        _lib.check(st, "lapack::engine::_poerr_batched")
+
+    @staticmethod
+    def _poerr_vbatched(plan, matrixA, matrixR, matrixB, matrixX, nrhs, ldb, ldx, batch, info, ferr, berr, lde, srcPackage, stream=None):
+        """The same for the blocks of a cap_vbatch_plan (n_i <= 256; a plan refuses larger blocks when it is made) with the stacked matrixB /
+        matrixX of _potrs_vbatched: cap_dpoerr_vbatched, one launch per non-empty size class for berr alone, four with ferr; the rows of
+        empty blocks are not written.  Asynchronous."""
+        engine._colmajor(srcPackage)
+        L = _lib.lib()
+        work = scratch(L.cap_dpoerr_vbatched_work_size(plan, nrhs), matrixX) if ferr is not None else None
+        st = L.cap_dpoerr_vbatched(plan, int(srcPackage.uplo), nrhs, dptr(matrixA), dptr(matrixR), dptr(matrixB), ldb, dptr(matrixX), ldx,
+                                   engine._batched_info(info, batch), engine._out_ptr(ferr, batch * lde, "ferr"),
+                                   engine._out_ptr(berr, batch * lde, "berr"), lde, dptr(work), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_poerr_vbatched")
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

@@ -397,6 +397,90 @@ int cap_dsyrk_batched(int uplo, int trans, int64_t n, int64_t k, double alpha, c
 int cap_dsyrk_vbatched(const cap_vbatch_plan* p, int uplo, int trans, int64_t k, double alpha, const double* V, int64_t ldv, double beta,
                        double* C, const double* shift, int fill, void* stream);
 
+/* Batched products with the SYMMETRIC block itself and the diagnostics built on them (csrc/symm_batched.hip): what says how many digits of
+ * cap_dpotrs_batched's and cap_dpotri_batched's answers mean anything.  For every block
+ *   Y_i <- beta B_i + alpha A_i X_i,   0 <= n <= 256, any nrhs >= 0 (the passes over nrhs are inside the one launch), fp64, one GPU.
+ * A_i is the symmetric n x n block at A + i * stride_a (leading dimension lda) of which only the UPPER triangle of the column-major block
+ * holds data - the triangle cap_dpotrf_batched reads and cap_dsyrk_batched / cap_dpotri_batched write.  X_i, B_i, Y_i are n x nrhs
+ * column-major, the right-hand-side layout of cap_dpotrs_batched.  absolute = 1 takes |.| of every element of A, X and B on load.
+ * The arithmetic, the same on both paths: s_ij = sum_k a_ik x_kj over the symmetrised row (a_ik from (min, max) of the triangle) on the
+ * fp64 16 x 16 x 4 MFMA from a zero accumulator with K ascending (rows and columns >= n enter as +0.0 and are never addressed);
+ * t = alpha * s; out = (beta == 0) ? t : fma(beta, b, t), without contraction.  beta == 0 never reads B (it may be NULL); alpha == 0 never
+ * addresses A or X (they may be NULL).  The strictly lower triangle of A is never read, inside diagonal tiles too; rows n .. ld - 1, the gaps
+ * between blocks and everything behind the last block are never read or written.  Y is either EXACTLY B (the same pointer, ld and stride: in
+ * place) or disjoint from it; Y must not overlap A or X (refused).  A Y that overlaps B in any other way is not detected and gives undefined
+ * results.
+ * The contract is that of the batched entries above: ONE launch per call on a 1-D grid (n <= 64: a wavefront per 64 / NP blocks; above: a
+ * workgroup of four waves per block), one per occurring size class on a plan; no allocation, no memset, no atomics, no mutex, no helper
+ * stream, no host synchronisation, nothing between workgroups; asynchronous on `stream`; 64-bit offsets.
+ * cap_dlansy_batched: out[i] = |A_i|_1 = max_j sum_i |a_ij| (norm '1' / 'O' / 'I': by symmetry one number, as cap_dlansy) in ONE launch -
+ * the absolute product with a column of ones the kernel supplies itself, then the maximum.  A NaN in the triangle gives NaN.  It is the
+ * norm of the matrix BEFORE cap_dpotrf_batched overwrote it.
+ * cap_dpocon_batched: EXACT reciprocal condition numbers, not LAPACK's estimate (for blocks this small the inverse is cheaper than the
+ * estimator's dependent solves).  R holds the factors cap_dpotrf_batched[_blocked] left and is not written; anorm[i] is |A_i|_1 from
+ * cap_dlansy_batched.  The upper triangles are copied into work (cap_dpocon_batched_work_size(n, batch) = n n batch doubles),
+ * cap_dpotri_batched runs on the copy, the 1-norm pass runs on the result and rcond[i] = 1 / (anorm[i] * |A_i^-1|_1): one multiplication,
+ * one correctly rounded division.  anorm[i] == 0 -> 0; NaN -> NaN; info[i] != 0 (info may be NULL) -> NaN.  FOUR launches, whatever batch.
+ * cap_dpoerr_batched: the bounds of LAPACK's dporfs for the solutions X of A X = B (A: the matrix before the factorization, upper triangle;
+ * R: its factors; none of A, R, B, X is written).  berr[i * lde + j] = max_r of the guarded ratio of cap_dpoerr,
+ * |b - A x|_r / (|A||x| + |b|)_r (safe1 = (n + 1) safmin added to both where the denominator is <= safe2 = safe1 / eps; eps = 2^-53,
+ * safmin = 2^-1022); ferr[i * lde + j] = | |A_i^-1| w_j |_inf / |x_j|_inf (x_j = 0: the numerator alone) with w = |r| + (n + 1) eps
+ * (|A||x| + |b|) - one rounded multiplication, one rounded addition - and the COMPUTED inverse in place of an estimate of that norm.
+ * Either of ferr / berr may be NULL; berr alone needs no inverse, no copy and no work: ONE launch.  With ferr: FOUR launches (residual and
+ * weights; copy; cap_dpotri_batched on the copy; the absolute product with its row maxima), whatever batch and nrhs;
+ * cap_dpoerr_batched_work_size(n, nrhs, batch) = n (n + nrhs) batch doubles.  A block with info[i] != 0 gets NaN.  The outputs and work of
+ * cap_dlansy_batched, cap_dpocon_batched and cap_dpoerr_batched (out, rcond, ferr, berr, work) must be disjoint from one another and from
+ * every input (A, R, B, X, anorm, info); that is not checked, an overlap gives undefined results.
+ * THE BIT CONTRACTS.
+ *   1. PLAN = FIXED: every block of a plan call gets the bits of the fixed-size entry on it alone with batch = 1 - Y, the norm, rcond,
+ *      ferr and berr.
+ *   2. LAYOUT INDEPENDENCE: a block's bits are a function of (n, its data, alpha, beta, absolute) only - not of batch, index, any ld /
+ *      stride or the alignment.
+ *   3. COLUMN INDEPENDENCE: a column of Y, and its ferr / berr, do not depend on the columns that travel with it or on the pass it is in.
+ *   4. COMPOSITION: the norm equals the maximum of cap_dsymm_batched(absolute = 1) against ones; rcond equals 1 / (anorm * the norm of
+ *      cap_dpotri_batched on a copy of R); berr and ferr equal their formulas evaluated on the outputs of cap_dsymm_batched (r: alpha = -1,
+ *      beta = 1; |A||x| + |b|: absolute, alpha = beta = 1; |A^-1| w: absolute, alpha = 1, beta = 0), all bit for bit.
+ * Argument rules, in this order, all decided before any device call.  cap_dsymm_batched: absolute other than 0 / 1, n < 0, nrhs < 0,
+ * batch < 0; with n nrhs batch > 0: a NULL Y, a NULL A or X with alpha != 0, a NULL B with beta != 0; lda < n, ldx < n, ldy < n, with
+ * batch > 1 stride_a < lda n, stride_x < ldx nrhs, stride_y < ldy nrhs; with beta != 0 the same for ldb / stride_b; with alpha != 0 a Y that
+ * overlaps A or X -> CAP_ERR_ARG; then uplo = LOWER -> CAP_ERR_UNSUPPORTED; then n > 256 -> CAP_ERR_UNSUPPORTED; then a grid beyond one
+ * dimension (2^31 - 1 workgroups) -> CAP_ERR_UNSUPPORTED; then n == 0, nrhs == 0 or batch == 0 -> CAP_OK without a launch.
+ * cap_dlansy_batched: n < 0, batch < 0; a NULL A or out with n batch > 0; lda / stride_a -> CAP_ERR_ARG; an unknown norm ->
+ * CAP_ERR_UNSUPPORTED; then LOWER, n > 256, the grid, the empty call as above.  cap_dpocon_batched: n < 0, batch < 0; a NULL R, anorm, rcond
+ * or work with n batch > 0; ldr / stride_r -> CAP_ERR_ARG; then as above.  cap_dpoerr_batched: n < 0, nrhs < 0, batch < 0; with
+ * n nrhs batch > 0 and ferr or berr given: a NULL A, B or X, with ferr a NULL R or work; lda / stride_a, with ferr ldr / stride_r, ldb /
+ * stride_b, ldx / stride_x; with ferr or berr given lde < nrhs -> CAP_ERR_ARG; then as above (nothing to do: n, nrhs or batch 0, or both
+ * outputs NULL).
+ * The _vbatched forms: the same on a cap_vbatch_plan.  A, R are flat tensors with the plan's offsets and leading dimensions; X, B, Y are
+ * the STACKED system of cap_dpotrs_vbatched ((sum n_i) x nrhs, ld >= sum n_i); out, anorm, info, rcond have `batch` entries in batch order,
+ * ferr / berr batch x lde; the entries of empty blocks are neither read nor written.  Launches: cap_dsymm_vbatched and
+ * cap_dlansy_vbatched ONE per occurring size class; cap_dpocon_vbatched THREE per class plus ONE (work: the plan's CAP_VBATCH_TOTAL
+ * doubles = cap_dpocon_vbatched_work_size); cap_dpoerr_vbatched ONE per class for berr alone, FOUR per class with ferr (work: CAP_VBATCH_TOTAL
+ * + (sum n_i) nrhs doubles = cap_dpoerr_vbatched_work_size).  Entry rules, in this order: a NULL plan, bad absolute, nrhs < 0; NULL pointers
+ * when something would be launched (as above); a leading dimension of a stacked operand < sum n_i, lde < nrhs; a Y that overlaps A or X ->
+ * CAP_ERR_ARG; an unknown norm, uplo = LOWER -> CAP_ERR_UNSUPPORTED; nothing to launch -> CAP_OK; a plan made without a device ->
+ * CAP_ERR_HIP.                                                                                                                          */
+int cap_dsymm_batched(int uplo, int absolute, int64_t n, int64_t nrhs, double alpha, const double* A, int64_t lda, int64_t stride_a,
+                      const double* X, int64_t ldx, int64_t stride_x, double beta, const double* B, int64_t ldb, int64_t stride_b, double* Y,
+                      int64_t ldy, int64_t stride_y, int64_t batch, void* stream);
+int cap_dsymm_vbatched(const cap_vbatch_plan* p, int uplo, int absolute, int64_t nrhs, double alpha, const double* A, const double* X,
+                       int64_t ldx, double beta, const double* B, int64_t ldb, double* Y, int64_t ldy, void* stream);
+int cap_dlansy_batched(int norm, int uplo, int64_t n, const double* A, int64_t lda, int64_t stride_a, int64_t batch, double* out, void* stream);
+int cap_dlansy_vbatched(const cap_vbatch_plan* p, int norm, int uplo, const double* A, double* out, void* stream);
+int64_t cap_dpocon_batched_work_size(int64_t n, int64_t batch);
+int64_t cap_dpocon_vbatched_work_size(const cap_vbatch_plan* p);
+int cap_dpocon_batched(int uplo, int64_t n, const double* R, int64_t ldr, int64_t stride_r, int64_t batch, const double* anorm, const int* info,
+                       double* rcond, double* work, void* stream);
+int cap_dpocon_vbatched(const cap_vbatch_plan* p, int uplo, const double* R, const double* anorm, const int* info, double* rcond, double* work,
+                        void* stream);
+int64_t cap_dpoerr_batched_work_size(int64_t n, int64_t nrhs, int64_t batch);
+int64_t cap_dpoerr_vbatched_work_size(const cap_vbatch_plan* p, int64_t nrhs);
+int cap_dpoerr_batched(int uplo, int64_t n, int64_t nrhs, const double* A, int64_t lda, int64_t stride_a, const double* R, int64_t ldr,
+                       int64_t stride_r, const double* B, int64_t ldb, int64_t stride_b, const double* X, int64_t ldx, int64_t stride_x,
+                       int64_t batch, const int* info, double* ferr, double* berr, int64_t lde, double* work, void* stream);
+int cap_dpoerr_vbatched(const cap_vbatch_plan* p, int uplo, int64_t nrhs, const double* A, const double* R, const double* B, int64_t ldb,
+                        const double* X, int64_t ldx, const int* info, double* ferr, double* berr, int64_t lde, double* work, void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
