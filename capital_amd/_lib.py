@@ -64,6 +64,8 @@ SIGNATURES = {
     "cap_dpoerr_vbatched_work_size": (i64, [ptr, i64]),
     "cap_dpoerr_batched": (cint, [cint, i64, i64, ptr, i64, i64, ptr, i64, i64, ptr, i64, i64, ptr, i64, i64, i64, ptr, ptr, ptr, i64, ptr, ptr]),
     "cap_dpoerr_vbatched": (cint, [ptr, cint, i64, ptr, ptr, ptr, i64, ptr, i64, ptr, ptr, ptr, i64, ptr, ptr]),
+    "cap_dpstrf_batched": (cint, [cint, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, ptr, ptr, ptr, ptr, ptr, i64, ptr]),
+    "cap_dpstrf_vbatched": (cint, [ptr, cint, i64, dbl, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr]),
     "cap_dtrtri": (cint, [cint, i64, ptr, i64, ptr, ptr]),
     "cap_dtrtri_work_size": (i64, [i64]),
     "cap_dlauum": (cint, [cint, i64, ptr, i64, ptr, i64, ptr]),

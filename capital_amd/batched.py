@@ -17,6 +17,9 @@ symm / norm1 / rcond / error_bounds (and the VarBatch forms): how many digits of
 block itself from the triangle potrf reads, its 1-norm, the EXACT reciprocal condition number and the forward / backward error bounds of
 a solve, from the computed inverse (cap_dsymm_batched / cap_dlansy_batched / cap_dpocon_batched / cap_dpoerr_batched and their _vbatched
 forms, csrc/symm_batched.hip).
+pstrf / permute (and the VarBatch forms): the PIVOTED factorization for blocks that are semidefinite or numerically rank deficient, n <= 64 -
+rank, a factor that survives zero pivots, the trace error and the pseudo-log-determinant, one launch (cap_dpstrf_batched /
+cap_dpstrf_vbatched, csrc/pstrf_batched.hip) - and its permutation applied to right-hand sides.
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
@@ -43,6 +46,8 @@ _PACK_E = lapack.ArgPack_poerr_batched(lapack.Order.AlapackColumnMajor, lapack.U
 _PACK_VN = lapack.ArgPack_lansy_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper, '1')
 _PACK_VC = lapack.ArgPack_pocon_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_VE = lapack.ArgPack_poerr_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_P = lapack.ArgPack_pstrf_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_VP = lapack.ArgPack_pstrf_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 
 
 def _check(t, name, dims):
@@ -409,6 +414,63 @@ def error_bounds(A, R, B, X, info=None, ferr=True):
     return shape(fe), shape(be)
 
 
+def _pstrf_args(max_rank, nmax, tol):
+    """(max_rank, tol) of a pivoted call, checked; nmax: the largest block"""
+    if nmax > lapack.BATCHED_SMALL_MAX:
+        raise _lib.CapitalError("pstrf handles blocks of up to %d rows, got %d - use cholinv.factor_pivoted on each block"
+                                % (lapack.BATCHED_SMALL_MAX, nmax))
+    mr = nmax if max_rank is None else int(max_rank)
+    if mr < 0 or (max_rank is not None and mr > nmax):
+        raise _lib.CapitalError("max_rank must lie in 0 .. %d, got %s" % (nmax, max_rank))
+    tol = float(tol)
+    if tol != tol:
+        raise _lib.CapitalError("tol is NaN")
+    return mr, tol
+
+
+def pstrf(A, max_rank=None, tol=-1.0, logdet=False):
+    """PIVOTED Cholesky factors of a batch of symmetric positive SEMIdefinite blocks, one launch: for blocks that are rank deficient, where
+    potrf gives info != 0 and NaN.  A: fp64 device tensor of shape (batch, n, n), n <= 64, under potrf's layout rules; only the triangle
+    potrf reads is read (the LOWER triangle of A[i] in torch's reading) and A is not written.  At most max_rank steps per block (None: n);
+    a block stops earlier at the first pivot <= tol (tol < 0: n 2^-53 max_i a_ii of that block, LAPACK's default; otherwise absolute).
+    Returns (L, piv, rank, resid, info), plus logdet with logdet=True:
+      L: a fresh (batch, n, max_rank) tensor whose torch reading is the dense lower-trapezoidal factor - L[i] @ L[i].T ~ A[i][piv[i]][:, piv[i]]
+        with explicit zeros above the diagonal and in the columns >= rank[i].  With max_rank = n it is a valid R argument of trmm / trsm /
+        potrs / potri / syrk(trans=True) (a block of rank < n has zeros on its diagonal: trmm and syrk are fine, the solves are not);
+      piv: int64 (batch, n), the chosen pivots in order, then the unselected indices ascending - usable as a torch.gather index (permute);
+      rank: int32 (batch,), the steps done; resid: fp64 (batch,), trace(A[i] - L L^T) of the permuted block, the sum of the remaining diagonal;
+      info: int32 (batch,) with the meaning of cap_dpstrf - 0: stopped at a pivot <= tol (or after n steps), 1: max_rank steps done with
+        the remainder above tol, 2: a NaN on the remaining diagonal (rank = the steps done, those columns of L are intact).  It is NOT the
+        info that trsm, trmm or potrs expect: pass (info == 2).int() there if a guard is wanted;
+      logdet: fp64 (batch,), 2 sum_{j < rank} log l_jj - the pseudo-log-determinant a degenerate Gaussian needs; NaN for info 2.
+    A block's bits depend on (n, max_rank, tol, its data) alone.  n > 64 raises CapitalError: use cholinv.factor_pivoted per block.
+    Asynchronous on the current stream; nothing is read back."""
+    batch, n, lda, stride = _blocks(A, "A")
+    mr, tol = _pstrf_args(max_rank, n, tol)
+    L = torch.zeros((batch, n, mr), dtype=torch.float64, device=A.device)
+    piv = torch.zeros((batch, n), dtype=torch.int64, device=A.device)
+    rank, resid, info, ld = lapack.engine._pstrf_batched(A, L if L.numel() else None, piv, n, mr, lda, stride, max(mr, 1), n * mr, batch, tol,
+                                                         _PACK_P, want_logdet=bool(logdet))
+    return (L, piv, rank, resid, info, ld) if logdet else (L, piv, rank, resid, info)
+
+
+def permute(B, piv, inverse=False):
+    """The pivoting of pstrf applied to right-hand sides (torch only: a gather / scatter along the last dimension).  B: (batch, nrhs, n) or
+    (batch, n); piv: what pstrf returned.  inverse=False: out[i, ..., k] = B[i, ..., piv[i, k]] - b in the pivoted order; inverse=True:
+    out[i, ..., piv[i, k]] = B[i, ..., k] - back to the natural order.  So, for full-rank blocks,
+    permute(potrs(L, permute(B, piv)), piv, inverse=True) solves A x = b, and permute(trmm(L, z), piv, inverse=True) samples N(0, A_i) for
+    semidefinite ones.  Returns a fresh tensor."""
+    if not isinstance(B, torch.Tensor) or not isinstance(piv, torch.Tensor) or B.dim() not in (2, 3) or piv.dim() != 2:
+        raise _lib.CapitalError("B must be (batch, nrhs, n) or (batch, n) and piv (batch, n)")
+    if piv.dtype != torch.int64 or piv.device != B.device or piv.shape[0] != B.shape[0] or piv.shape[1] != B.shape[-1]:
+        raise _lib.CapitalError("piv must be an int64 (batch, n) tensor on B's device with B's batch and n, got shape %s for B of shape %s"
+                                % (tuple(piv.shape), tuple(B.shape)))
+    idx = piv if B.dim() == 2 else piv.unsqueeze(1).expand(B.shape)
+    if inverse:
+        return torch.empty_like(B, memory_format=torch.contiguous_format).scatter_(-1, idx, B)
+    return torch.gather(B, -1, idx)
+
+
 class VarBatch:
     """A batch of SPD blocks of DIFFERENT sizes 0 <= n_i <= 256 inside ONE flat fp64 device tensor: block i is the n_i x n_i column-major block
     at element offsets[i] with leading dimension ld[i].  sizes, ld, offsets: host sequences of ints; ld=None: ld[i] = max(n_i, 1);
@@ -660,6 +722,43 @@ class VarBatch:
         lapack.engine._poerr_vbatched(self._plan, A, R, B2, X2, nrhs, ldb, ldx, self.batch, _info(info, R), fe, be, lde, _PACK_VE)
         shape = lambda t: None if t is None else (t[:self.batch, 0] if X.dim() == 1 else t[:self.batch, :nrhs])
         return shape(fe), shape(be)
+
+    def pstrf(self, A, max_rank=None, tol=-1.0, logdet=False):
+        """PIVOTED Cholesky factors of all blocks (every n_i <= 64), one launch per size class, as pstrf of this module.  A: the flat
+        tensor; of every block only the triangle potrf reads is read (the LOWER one in torch's reading, .block) and A is not written.  The
+        cap of block i is min(max_rank, n_i) (None: no cap).  Returns (R, piv, rank, resid, info), plus logdet with logdet=True:
+        R: a fresh flat tensor in the plan's layout - .block(R, i) reads as the n_i x n_i lower-triangular L_i with
+        L_i L_i^T ~ A_i[piv_i][:, piv_i] and zero columns >= rank[i]; every entry of every block is written, padding and gaps are zero.
+        piv: the stacked int64 (rows,) vector of block-local indices, block i at row_offsets[i] (VarBatch.permute applies it).
+        rank, resid, info, logdet: (batch,) in batch order, 0 for an empty block.  info is 0 / 1 / 2 as for cap_dpstrf - NOT the info
+        that trsm, trmm or potrs expect; pass (info == 2).int() there if a guard is wanted.  Every block gets the bits of the fixed-size
+        pstrf on it alone.  A plan whose largest block exceeds 64 raises CapitalError: use cholinv.factor_pivoted per block.
+        Asynchronous on the current stream; nothing is read back."""
+        nmax = max(self.sizes, default=0)
+        mr, tol = _pstrf_args(None if max_rank is None else min(max(int(max_rank), -1), nmax), nmax, tol)     # (a cap above n_i is n_i)
+        self._flat(A, "A")
+        R = torch.zeros(max(self.total, 1), dtype=torch.float64, device=A.device)[:self.total]
+        piv = torch.zeros(max(self.rows, 1), dtype=torch.int64, device=A.device)[:self.rows]
+        rank, resid, info, ld = lapack.engine._pstrf_vbatched(self._plan, A, R, piv, self.rows, nmax, mr, self.batch, tol, _PACK_VP,
+                                                              want_logdet=bool(logdet))
+        return (R, piv, rank, resid, info, ld) if logdet else (R, piv, rank, resid, info)
+
+    def permute(self, B, piv, inverse=False):
+        """The pivoting of VarBatch.pstrf applied to stacked vectors (torch only).  B: (rows,) or (nrhs, rows); piv: the stacked
+        block-local indices pstrf returned.  inverse=False: entry row_offsets[i] + k of the result is entry row_offsets[i] + piv_i[k] of B;
+        inverse=True undoes it.  Returns a fresh tensor."""
+        if (not isinstance(B, torch.Tensor) or not isinstance(piv, torch.Tensor) or B.dim() not in (1, 2) or piv.dim() != 1
+                or piv.dtype != torch.int64 or piv.shape[0] != self.rows or B.shape[-1] != self.rows or piv.device != B.device):
+            raise _lib.CapitalError("B must be (rows,) or (nrhs, rows) and piv an int64 (rows,) tensor on its device, rows = %d" % self.rows)
+        base = getattr(self, "_row_base", None)
+        if base is None or base.device != B.device:
+            host = [r for r, n in zip(self.row_offsets, self.sizes) for _ in range(n)]
+            base = self._row_base = torch.tensor(host, dtype=torch.int64).to(B.device)
+        idx = piv + base
+        idx = idx if B.dim() == 1 else idx.unsqueeze(0).expand(B.shape)
+        if inverse:
+            return torch.empty_like(B, memory_format=torch.contiguous_format).scatter_(-1, idx, B)
+        return torch.gather(B, -1, idx)
 
     def block(self, A, i):
         """The n_i x n_i view of block i of the flat tensor A in torch's row-major reading: block(A, i)[r, c] is element (c, r) of the

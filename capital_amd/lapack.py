@@ -7,7 +7,8 @@ _potri_batched (the factor, solve, triangular inverse and SPD inverse of many sm
 _potrs_vbatched / _potri_vbatched (the same for blocks of different sizes, described by a cap_vbatch_plan) and _cholupdate_batched /
 _cholupdate_vbatched (the rank-k update / downdate of those factors) and _trsm_batched / _trmm_batched / _trsm_vbatched / _trmm_vbatched
 (one triangular solve or product with those factors) and _lansy_batched / _pocon_batched / _poerr_batched with their _vbatched forms (the
-1-norms, the exact reciprocal condition numbers and the solve error bounds of those blocks) have no counterpart upstream.
+1-norms, the exact reciprocal condition numbers and the solve error bounds of those blocks) and _pstrf_batched / _pstrf_vbatched (the
+pivoted factorization of semidefinite blocks of up to 64 rows) have no counterpart upstream.
 _potrf / _trtri run on the GPU (wavefront-cooperative in-LDS leaves + MFMA GEMM recursion).
 Unlike upstream (which drops LAPACKE's return value, lapack/interface.hpp:39,54) _potrf
 returns `info`.  _geqrf / _orgqr are never called by any upstream algorithm
@@ -66,6 +67,8 @@ class Method(enum.IntEnum):
     AlapackLansyVbatched = 0x1B        # extension: not in the reference's enum
     AlapackPoconVbatched = 0x1C        # extension: not in the reference's enum
     AlapackPoerrVbatched = 0x1D        # extension: not in the reference's enum
+    AlapackPstrfBatched = 0x1E         # extension: not in the reference's enum
+    AlapackPstrfVbatched = 0x1F        # extension: not in the reference's enum
 
 
 class ArgPack_potrf:
@@ -227,6 +230,18 @@ class ArgPack_pocon_vbatched:
 class ArgPack_poerr_vbatched:
     def __init__(self, order, uplo):
         self.method = Method.AlapackPoerrVbatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_pstrf_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPstrfBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_pstrf_vbatched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPstrfVbatched
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
@@ -642,6 +657,70 @@ class engine:
                                    engine._batched_info(info, batch), engine._out_ptr(ferr, batch * lde, "ferr"),
                                    engine._out_ptr(berr, batch * lde, "berr"), lde, dptr(work), cur_stream(stream))
         _lib.check(st, "lapack::engine::_poerr_vbatched")
+
+    @staticmethod
+    def _pstrf_outputs(matrixA, matrixR, piv, count, batch, want_logdet):
+        """the checks and the zeroed per-block result tensors the two pivoted entries share: (rank, resid, info, logdet)"""
+        if not isinstance(matrixA, torch.Tensor) or not matrixA.is_cuda or matrixA.dtype != torch.float64:
+            raise _lib.CapitalError("matrixA must be an fp64 device tensor - there is no CPU path")
+        if matrixR is not None:
+            if not isinstance(matrixR, torch.Tensor) or not matrixR.is_cuda or matrixR.dtype != torch.float64 or matrixR.device != matrixA.device:
+                raise _lib.CapitalError("matrixR must be an fp64 device tensor on matrixA's device")
+            if matrixA.numel() > 0 and matrixR.numel() > 0:
+                span = lambda t: (t.data_ptr(), t.data_ptr() + 8 * (sum((d - 1) * abs(s) for d, s in zip(t.shape, t.stride())) + 1))
+                (a0, a1), (r0, r1) = span(matrixA), span(matrixR)
+                if a0 < r1 and r0 < a1:
+                    raise _lib.CapitalError("matrixR overlaps matrixA")
+        if (not isinstance(piv, torch.Tensor) or not piv.is_cuda or piv.dtype != torch.int64 or piv.numel() < count or not piv.is_contiguous()
+                or piv.device != matrixA.device):
+            raise _lib.CapitalError("piv must be a contiguous int64 device tensor of %d entries on matrixA's device" % count)
+        dev = matrixA.device
+        rank = torch.zeros(max(batch, 1), dtype=torch.int32, device=dev)
+        info = torch.zeros(max(batch, 1), dtype=torch.int32, device=dev)
+        resid = torch.zeros(max(batch, 1), dtype=torch.float64, device=dev)
+        logdet = torch.zeros(max(batch, 1), dtype=torch.float64, device=dev) if want_logdet else None
+        return rank, resid, info, logdet
+
+    @staticmethod
+    def _pstrf_batched(matrixA, matrixR, piv, n, max_rank, lda, stride_a, ldr, stride_r, batch, tol, srcPackage, want_logdet=False, stream=None):
+        """Pivoted Cholesky of the symmetric positive semidefinite n x n blocks (n <= 64, column-major, ld lda; upper triangles read, nothing
+        of them written) at matrixA + i stride_a, i < batch, in at most max_rank steps each, in one launch (cap_dpstrf_batched):
+        A_i[piv_i][:, piv_i] ~ R_i^T R_i with R_i max_rank x n (ld ldr) at matrixR + i stride_r and piv a contiguous int64 device tensor of
+        batch n entries.  tol < 0: n eps max_i a_ii per block, otherwise absolute.  matrixR must not overlap matrixA.  Returns
+        (rank, resid, info, logdet): int32 / fp64 / int32 device tensors of batch entries and, with want_logdet, the fp64
+        pseudo-log-determinants 2 sum_{j < rank} log r_jj (else None).  info is 0 / 1 / 2 as for _pstrf - stopped at a pivot <= tol, the
+        cap was hit, a NaN on the remaining diagonal - NOT the info _potrs_batched, _trsm_batched or _trmm_batched expect.  Blocks above
+        64 rows: cholinv.factor_pivoted, one block at a time.  Nothing is read back: asynchronous."""
+        engine._colmajor(srcPackage)
+        if n > BATCHED_SMALL_MAX:
+            raise _lib.CapitalError("the batched pivoted factorization handles blocks of up to %d rows, got n = %d - use "
+                                    "cholinv.factor_pivoted on each block" % (BATCHED_SMALL_MAX, n))
+        rank, resid, info, logdet = engine._pstrf_outputs(matrixA, matrixR, piv, batch * n, batch, want_logdet)
+        st = _lib.lib().cap_dpstrf_batched(int(srcPackage.uplo), n, max_rank, float(tol), dptr(matrixA), lda, stride_a, dptr(matrixR), ldr,
+                                           stride_r, piv.data_ptr(), rank.data_ptr(), resid.data_ptr(),
+                                           logdet.data_ptr() if want_logdet else None, info.data_ptr(), batch, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_pstrf_batched")
+        cut = lambda t: None if t is None else t[:max(batch, 0)]
+        return cut(rank), cut(resid), cut(info), cut(logdet)
+
+    @staticmethod
+    def _pstrf_vbatched(plan, matrixA, matrixR, piv, rows, nmax, max_rank, batch, tol, srcPackage, want_logdet=False, stream=None):
+        """The same for the blocks of a cap_vbatch_plan whose largest block has at most 64 rows (nmax: the plan's largest n; rows: sum n_i):
+        cap_dpstrf_vbatched, one launch per non-empty size class.  matrixA, matrixR: two flat tensors in the plan's layout - matrixR gets
+        every entry of every n_i x n_i block, the cap of block i is min(max_rank, n_i); piv: the stacked int64 vector of `rows` block-local
+        indices.  Returns (rank, resid, info, logdet) in batch order as _pstrf_batched does; the entries of empty blocks are 0.  Blocks above
+        64 rows: cholinv.factor_pivoted.  Asynchronous."""
+        engine._colmajor(srcPackage)
+        if nmax > BATCHED_SMALL_MAX:
+            raise _lib.CapitalError("the batched pivoted factorization handles blocks of up to %d rows, the plan's largest has %d - use "
+                                    "cholinv.factor_pivoted on each block" % (BATCHED_SMALL_MAX, nmax))
+        rank, resid, info, logdet = engine._pstrf_outputs(matrixA, matrixR, piv, rows, batch, want_logdet)
+        st = _lib.lib().cap_dpstrf_vbatched(plan, int(srcPackage.uplo), max_rank, float(tol), dptr(matrixA), dptr(matrixR), piv.data_ptr(),
+                                            rank.data_ptr(), resid.data_ptr(), logdet.data_ptr() if want_logdet else None, info.data_ptr(),
+                                            cur_stream(stream))
+        _lib.check(st, "lapack::engine::_pstrf_vbatched")
+        cut = lambda t: None if t is None else t[:max(batch, 0)]
+        return cut(rank), cut(resid), cut(info), cut(logdet)
 
     @staticmethod
     def _trtri(matrixA, n, lda, srcPackage, stream=None):

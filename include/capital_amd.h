@@ -481,6 +481,54 @@ int cap_dpoerr_batched(int uplo, int64_t n, int64_t nrhs, const double* A, int64
 int cap_dpoerr_vbatched(const cap_vbatch_plan* p, int uplo, int64_t nrhs, const double* A, const double* R, const double* B, int64_t ldb,
                         const double* X, int64_t ldx, const int* info, double* ferr, double* berr, int64_t lde, double* work, void* stream);
 
+/* Batched PIVOTED Cholesky factorization for symmetric positive SEMIdefinite blocks of up to 64 rows (csrc/pstrf_batched.hip): cap_dpstrf
+ * on every block of a batch in ONE launch - numerical rank, a factor that survives zero pivots, the trace error of the low-rank
+ * approximation - where cap_dpotrf_batched turns a block into NaN at the first pivot that is not > 0.  For every block
+ *   A_i[piv_i][:, piv_i] ~ R_i^T R_i,   1 <= n <= 64, 0 <= max_rank <= n, fp64, one GPU.
+ * A_i is the n x n column-major block at A + i * stride_a (leading dimension lda); only its UPPER triangle is read (the strictly lower one
+ * may hold anything) and A is never written.  R_i is max_rank x n column-major at R + i * stride_r with ldr >= max(max_rank, 1) and, for
+ * batch > 1, stride_r >= ldr n.  R MUST NOT OVERLAP A: that is not checked, an overlap gives undefined results.  piv is batch x n int64,
+ * block i at piv + i n, 0-based; rank (required) and info (may be NULL) are int32 per block; resid and logdet are doubles per block and may
+ * be NULL.
+ * The steps are those of cap_dpstrf, per block.  d = the remaining diagonal (initially diag A_i).  In front of step j = 0, 1, ...: p = the
+ * unselected index of largest d (ties: the lowest index).  A NaN among the unselected d: stop, info = 2.  No unselected index, or
+ * !(d[p] > tol_used): stop, info = 0.  j = max_rank: stop, info = 1.  tol_used = tol < 0 ? n 2^-53 max_i a_ii : tol, formed in front of step
+ * 0.  Otherwise, THE STATED RECURRENCE: for each unselected c != p, t = A(p, c); t = fma(-W[i, p], W[i, c], t) for i = 0 .. j - 1 in
+ * ascending order; r = t / sqrt(d[p]); W[j, c] = r; d[c] = fma(-r, r, d[c]); W[j, p] = sqrt(d[p]); W[j, c] = +0.0 for the columns chosen
+ * earlier - the square root and the division correctly rounded.  (cap_dpstrf forms the same sums in another order: its bits differ.)
+ * Results: rank[i] = the steps done; piv_i = the chosen pivots in order, then the unselected indices in increasing order - always a
+ * permutation; R_i[:, k] = W[:, piv_i[k]] with rows rank .. max_rank - 1 equal to +0.0: the WHOLE max_rank x n rectangle of every block is
+ * written, rows >= max_rank, padding and gaps are not touched; resid[i] = s after s = 0; s += d[c] over the unselected c in ascending
+ * order = trace(A_i - R_i^T R_i); logdet[i] = 2 sum_{j < rank} log r_jj added in ascending j as cap_dpotrf_batched does - the
+ * pseudo-log-determinant of a degenerate Gaussian - and NaN for info = 2; info[i] as above.  info = 2 is a result, not an error: the call
+ * returns CAP_OK, rank = the steps done and the finished rows of R are intact.  max_rank = 0 is legal: rank 0, the identity piv, resid =
+ * trace A_i, info 0 or 1.  NOTE: this info (0 / 1 / 2) is NOT the info of cap_dpotrf_batched that cap_dpotrs_batched, cap_dtrsm_batched and
+ * cap_dtrmm_batched expect.
+ * THE BIT CONTRACT: a block's bits - R, piv, rank, resid, logdet, info - depend on (n, max_rank, tol, its data) alone.  They do not depend
+ * on batch, the block's index, lda / ldr, the strides, the alignment or the blocks that share its wave.  PLAN = FIXED: cap_dpstrf_vbatched
+ * gives every block the bits of cap_dpstrf_batched on it alone with n = n_i, max_rank = min(max_rank, n_i) and batch = 1.
+ * The contract is that of the batched entries above: ONE launch per call on a 1-D grid (a wavefront per 64 / NP blocks, NP = 8, 16, 32 or
+ * 64 >= n), one per occurring size class on a plan; no work argument, no allocation, no memset, no atomics, no mutex, no helper stream, no
+ * host synchronisation, nothing between workgroups; asynchronous on `stream`; 64-bit offsets.
+ * Argument rules, in this order, all decided before any device call.  n < 0, batch < 0, max_rank < 0, max_rank > n, a NaN tol ->
+ * CAP_ERR_ARG; with n batch > 0: a NULL A, piv or rank, with max_rank > 0 a NULL R; lda < n, with batch > 1 stride_a < lda n; with
+ * max_rank > 0: ldr < max_rank, with batch > 1 stride_r < ldr n -> CAP_ERR_ARG; then uplo = LOWER -> CAP_ERR_UNSUPPORTED (as cap_dpstrf: in
+ * front of the empty case); then n > 64 (use cap_dpstrf per block) -> CAP_ERR_UNSUPPORTED; then a grid beyond one dimension (2^31 - 1
+ * workgroups) -> CAP_ERR_UNSUPPORTED, nothing written; then n == 0 or batch == 0 -> CAP_OK, nothing touched.
+ * cap_dpstrf_vbatched: the same on a cap_vbatch_plan.  A and R are two flat tensors in the plan's own layout (offsets and leading
+ * dimensions); R gets EVERY entry of every n_i x n_i block (rows >= rank are +0.0), padding and gaps are untouched; the cap of block i is
+ * min(max_rank, n_i).  piv is the stacked vector of sum n_i block-local 0-based indices, block i at the prefix sum of n in batch order
+ * (the rows of cap_dpotrs_vbatched's right-hand sides); rank, resid, logdet, info have `batch` entries in batch order, and the entries of
+ * empty blocks are neither read nor written (capital_amd.batched hands out zeros for them).  ONE launch per occurring size class.  Entry
+ * rules, in this order: a NULL plan, max_rank < 0, a NaN tol; with a non-empty plan a NULL A, piv or rank, with max_rank > 0 a NULL R ->
+ * CAP_ERR_ARG; uplo = LOWER -> CAP_ERR_UNSUPPORTED; a plan whose largest block exceeds 64 -> CAP_ERR_UNSUPPORTED, nothing written; nothing
+ * to launch -> CAP_OK; a plan made without a device -> CAP_ERR_HIP.  (With max_rank = 0 a NULL R is legal and nothing of R is written.)      */
+int cap_dpstrf_batched(int uplo, int64_t n, int64_t max_rank, double tol, const double* A, int64_t lda, int64_t stride_a, double* R,
+                       int64_t ldr, int64_t stride_r, int64_t* piv, int* rank, double* resid, double* logdet, int* info, int64_t batch,
+                       void* stream);
+int cap_dpstrf_vbatched(const cap_vbatch_plan* p, int uplo, int64_t max_rank, double tol, const double* A, double* R, int64_t* piv, int* rank,
+                        double* resid, double* logdet, int* info, void* stream);
+
 /* Y = beta opB(B) + alpha op(A) opX(X) for a SYMMETRIC n x n A of which only the upper triangle holds data, and a thin block: X, B, Y are
  * n x nrhs, column-major device memory (not in the reference; the product behind cap_dlansy and the residuals of cap_dpoerr).  absolute = 1
  * takes |.| of every element of A, X and B before use (|A||X| + |B|); absolute = 0 uses them as they are.
