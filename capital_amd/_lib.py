@@ -52,6 +52,9 @@ SIGNATURES = {
     "cap_dtrmm_vbatched": (cint, [ptr, cint, cint, i64, ptr, ptr, i64, ptr, ptr]),
     "cap_dsyrk_batched": (cint, [cint, cint, i64, i64, dbl, ptr, i64, i64, dbl, ptr, i64, i64, ptr, cint, i64, ptr]),
     "cap_dsyrk_vbatched": (cint, [ptr, cint, cint, i64, dbl, ptr, i64, dbl, ptr, ptr, cint, ptr]),
+    "cap_dgemm_batched": (cint, [cint, cint, i64, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, dbl, ptr, i64, i64, i64, ptr]),
+    "cap_dgemm_vbatched_inner": (cint, [ptr, i64, i64, dbl, ptr, i64, ptr, i64, dbl, ptr, i64, i64, ptr]),
+    "cap_dgemm_vbatched_combine": (cint, [ptr, i64, i64, dbl, ptr, i64, ptr, i64, i64, dbl, ptr, i64, ptr]),
     "cap_dsymm_batched": (cint, [cint, cint, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, i64, ptr]),
     "cap_dsymm_vbatched": (cint, [ptr, cint, cint, i64, dbl, ptr, ptr, i64, dbl, ptr, i64, ptr, i64, ptr]),
     "cap_dlansy_batched": (cint, [cint, cint, i64, ptr, i64, i64, i64, ptr, ptr]),

@@ -20,6 +20,10 @@ forms, csrc/symm_batched.hip).
 pstrf / permute (and the VarBatch forms): the PIVOTED factorization for blocks that are semidefinite or numerically rank deficient, n <= 64 -
 rank, a factor that survives zero pivots, the trace error and the pseudo-log-determinant, one launch (cap_dpstrf_batched /
 cap_dpstrf_vbatched, csrc/pstrf_batched.hip) - and its permutation applied to right-hand sides.
+gemm (and VarBatch.inner / VarBatch.combine): the GENERAL product with two different operands, m, n <= 256, any k - the right-hand side
+X^T y of normal equations, cross terms W_1^T W_2 of two trsm results, V_i^T x and V_i z of low-rank-plus-block operators - one launch
+(cap_dgemm_batched / cap_dgemm_vbatched_inner, one launch for any plan / cap_dgemm_vbatched_combine, one per size class,
+csrc/gemm_batched.hip).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
@@ -312,6 +316,70 @@ def schur(R, B, C, info=None):
     return syrk(B, C, trans=True, alpha=-1.0, beta=1.0)
 
 
+def _gemm_pack(transa, transb, alpha, beta):
+    T = blas.Transpose
+    return blas.ArgPack_gemm(blas.Order.AblasColumnMajor, T.AblasTrans if transa else T.AblasNoTrans, T.AblasTrans if transb else T.AblasNoTrans,
+                             alpha, beta)
+
+
+def _matrices(t, name):
+    """(batch, rows, cols, ld, stride) of a (batch, rows, cols) tensor whose t[i] is row-major with a free stride(1) >= cols"""
+    _check(t, name, (3,))
+    batch, rows, cols = t.shape
+    if t.numel() == 0:                                   # nothing to address: the strides of an empty tensor say nothing
+        return batch, rows, cols, max(cols, 1), max(cols, 1) * rows
+    if cols > 1 and t.stride(2) != 1:
+        raise _lib.CapitalError("%s must have stride(-1) == 1, got strides %s" % (name, t.stride()))
+    ld = t.stride(1) if rows > 1 else max(cols, 1)
+    stride = t.stride(0)
+    if ld < cols or (batch > 1 and stride < ld * rows):
+        raise _lib.CapitalError("%s: blocks overlap (strides %s)" % (name, t.stride()))
+    return batch, rows, cols, ld, max(stride, 0)
+
+
+def _out_overlap(out, operands, alpha=1.0):
+    for t, name in operands:
+        (a0, a1), (b0, b1) = _span(t), _span(out)
+        if alpha != 0 and a0 < b1 and b0 < a1:
+            raise _lib.CapitalError("%s and the output overlap" % name)
+
+
+def gemm(A, B, C=None, transa=False, transb=False, alpha=1.0, beta=0.0):
+    """The general product of every pair of blocks, one launch, with torch.baddbmm's semantics:
+    C[i] <- alpha op(A[i]) @ op(B[i]) + beta C[i], op(M) = M or (transa / transb) M^T - right-hand sides X^T y of normal equations, cross
+    terms W_1^T W_2, V^T x and V z.  A, B, C: fp64 device tensors (batch, ., .) with stride(-1) == 1, a free stride(1) >= the last
+    dimension and non-overlapping blocks; op(A[i]) is m x k, op(B[i]) k x n, C is (batch, m, n) with m, n <= 256, any k.  C=None needs
+    beta == 0 and returns a fresh tensor.  beta == 0 does not read C (NaN there does not propagate).  A and B are not written; C must not
+    overlap A or B.  A row-major product is the column-major product with the operands swapped: that is what is handed to
+    cap_dgemm_batched, nothing is copied.  The summation order is fixed (csrc/gemm_batched.hip): every element is a function of its row of
+    op(A) and its column of op(B) alone, the same bits for any batch, layout or transposes.  Returns C.  Asynchronous on the current
+    stream."""
+    ba, ar, ac, lda, stride_a = _matrices(A, "A")
+    bb, br, bc, ldb, stride_b = _matrices(B, "B")
+    m, k = (ac, ar) if transa else (ar, ac)
+    kb, n = (bc, br) if transb else (br, bc)
+    if bb != ba or kb != k:
+        raise _lib.CapitalError("op(A) is (batch, m, k) and op(B) must be (batch, k, n) with batch = %d, k = %d, got shapes %s and %s"
+                                % (ba, k, tuple(A.shape), tuple(B.shape)))
+    if m > 256 or n > 256:
+        raise _lib.CapitalError("gemm takes outputs of at most 256 rows and columns, got m = %d, n = %d" % (m, n))
+    if B.device != A.device:
+        raise _lib.CapitalError("A and B live on different devices")
+    if C is None:
+        if beta != 0:
+            raise _lib.CapitalError("C=None needs beta == 0")
+        C = torch.zeros((ba, m, n), dtype=torch.float64, device=A.device)
+    cb, cm, cn, ldc, stride_c = _matrices(C, "C")
+    if (cb, cm, cn) != (ba, m, n):
+        raise _lib.CapitalError("C must be (batch, m, n) = (%d, %d, %d), got shape %s" % (ba, m, n, tuple(C.shape)))
+    if C.device != A.device:
+        raise _lib.CapitalError("A and C live on different devices")
+    _out_overlap(C, ((A, "A"), (B, "B")))
+    # row-major C = op(A) op(B)  <=>  column-major C^T = op(B)^T op(A)^T: the memory of B[i] is the first operand, with B's own flag
+    blas.engine._gemm_batched(B, A, C, n, m, k, ldb, stride_b, lda, stride_a, ldc, stride_c, ba, _gemm_pack(transb, transa, alpha, beta))
+    return C
+
+
 def _symm_pack(alpha, beta, absolute):
     return blas.ArgPack_symm(blas.Order.AblasColumnMajor, blas.UpLo.AblasUpper, alpha, beta, absolute)
 
@@ -478,6 +546,8 @@ class VarBatch:
     fixed-size kernels and lives on the device that is current when it is made; building and freeing it may synchronise, no other method
     does.  It is reusable for any number of calls, from several streams at once.  Every block gets, bit for bit, what the fixed-size
     functions of this module give for it alone - whichever blocks travel with it.
+    inner / combine work on the STACKED operands alone (no flat tensor): per-block products X_i^T Y_i of two stacked operands (one launch
+    for any plan, empty blocks give beta out[i]) and per-block combinations V_i Z_i back into a stacked result.
     .offsets / .row_offsets: tuples in batch order (row_offsets: the prefix sum of the sizes - the rows of the stacked right-hand sides);
     .total: elements the blocks span (the least length of A); .rows: sum of the sizes; .launches: launches per call.
     Overlapping blocks, negative sizes, ld[i] < n_i or a size above 256 raise CapitalError."""
@@ -655,6 +725,79 @@ class VarBatch:
         blas.engine._syrk_vbatched(self._plan, V2, C, k, ldv, self.batch, _syrk_pack(trans, alpha, beta), shift=_shift(shift, self.batch, C),
                                    fill=bool(symmetric))
         return C
+
+    def _rows_of(self, X, name, count):
+        """(X2, count, ldx) of a stacked operand (rows,) or (count, rows) with stride(-1) == 1 on the plan's device"""
+        _check(X, name, (1, 2))
+        X2 = X.unsqueeze(0) if X.dim() == 1 else X
+        if X2.shape[1] != self.rows:
+            raise _lib.CapitalError("%s must be (rows,) or (%s, rows) with rows = %d, got shape %s" % (name, count, self.rows, tuple(X.shape)))
+        if self.rows > 1 and X2.stride(1) != 1:
+            raise _lib.CapitalError("%s must have stride(-1) == 1, got strides %s" % (name, X.stride()))
+        ldx = X2.stride(0) if X2.shape[0] > 1 else max(self.rows, 1)
+        if ldx < self.rows:
+            raise _lib.CapitalError("%s: rows overlap (strides %s)" % (name, X.stride()))
+        if X.device.index != self.device:
+            raise _lib.CapitalError("%s lives on device %s, the plan on device %s" % (name, X.device.index, self.device))
+        return X2, X2.shape[0], ldx
+
+    def inner(self, X, Y, out=None, alpha=1.0, beta=0.0):
+        """The products of every block's rows of two stacked operands, ONE launch whatever the sizes:
+        out[i, a, b] <- alpha sum_{r in block i} X[a, r] Y[b, r] + beta out[i, a, b] - X_i^T y_i of normal equations, W_1^T W_2 from two trsm
+        results, V_i^T x.  X: (p, rows) or (rows,), Y: (q, rows) or (rows,), stacked as potrs takes B (stride(-1) == 1), p, q <= 256.  out:
+        fp64 device tensor (batch, p, q) with stride(-1) == 1 and non-overlapping blocks, or None (only with beta == 0) for a fresh one, in
+        which 1-D operands drop their axis.  An empty block is an empty sum and gives beta out[i] - unlike the other methods, which skip
+        empty blocks.  beta == 0 does not read out.  Every block gets the bits of gemm on its rows alone.  Returns out.  Asynchronous on
+        the current stream."""
+        X2, p, ldx = self._rows_of(X, "X", "p")
+        Y2, q, ldy = self._rows_of(Y, "Y", "q")
+        if p > 256 or q > 256:
+            raise _lib.CapitalError("inner takes at most 256 rows of X and of Y, got p = %d, q = %d" % (p, q))
+        fresh = out is None
+        if fresh:
+            if beta != 0:
+                raise _lib.CapitalError("out=None needs beta == 0")
+            out = torch.zeros((self.batch, p, q), dtype=torch.float64, device=X.device)
+        ob, op, oq, ldg, stride_g = _matrices(out, "out")
+        if (ob, op, oq) != (self.batch, p, q):
+            raise _lib.CapitalError("out must be (batch, p, q) = (%d, %d, %d), got shape %s" % (self.batch, p, q, tuple(out.shape)))
+        if out.device != X.device:
+            raise _lib.CapitalError("X and out live on different devices")
+        _out_overlap(out, ((X, "X"), (Y, "Y")), alpha)
+        # row-major out[i] (p x q) is the column-major q x p block Y_i^T X_i: Y is the first stacked operand
+        blas.engine._gemm_vbatched_inner(self._plan, Y2, X2, out, q, p, ldy, ldx, ldg, stride_g, _gemm_pack(True, False, alpha, beta))
+        if fresh:
+            if Y.dim() == 1:
+                out = out.squeeze(2)
+            if X.dim() == 1:
+                out = out.squeeze(1)
+        return out
+
+    def combine(self, Z, V, out=None, alpha=1.0, beta=0.0):
+        """Combinations of every block's vectors, one launch per size class:
+        out[b, row_offsets[i] + r] <- alpha sum_t Z[i, b, t] V[t, row_offsets[i] + r] + beta out[b, row_offsets[i] + r] - V_i z of low-rank
+        terms.  V: (k, rows) or (rows,) with stride(-1) == 1, as update takes it; Z: (batch, q, k) with stride(-1) == 1 and non-overlapping
+        blocks, q <= 256; out: (q, rows) with stride(-1) == 1, or None (only with beta == 0) for a fresh one.  Empty blocks are neither read
+        nor written.  beta == 0 does not read out.  Every block gets the bits of gemm on it alone.  Returns out.  Asynchronous on the
+        current stream."""
+        V2, k, ldv = self._rows_of(V, "V", "k")
+        zb, q, zk, ldz, stride_z = _matrices(Z, "Z")
+        if zb != self.batch or zk != k:
+            raise _lib.CapitalError("Z must be (batch, q, k) with batch = %d, k = %d, got shape %s" % (self.batch, k, tuple(Z.shape)))
+        if q > 256:
+            raise _lib.CapitalError("combine takes at most 256 rows of out, got q = %d" % q)
+        if Z.device != V.device:
+            raise _lib.CapitalError("V and Z live on different devices")
+        if out is None:
+            if beta != 0:
+                raise _lib.CapitalError("out=None needs beta == 0")
+            out = torch.zeros((q, self.rows), dtype=torch.float64, device=V.device)
+        if out.dim() != 2 or out.shape[0] != q:
+            raise _lib.CapitalError("out must be (q, rows) = (%d, %d), got shape %s" % (q, self.rows, tuple(out.shape)))
+        O2, _, ldc = self._rows_of(out, "out", "q")
+        _out_overlap(out, ((V, "V"), (Z, "Z")), alpha)
+        blas.engine._gemm_vbatched_combine(self._plan, V2, Z, O2, q, k, ldv, max(ldz, k, 1), stride_z, ldc, _gemm_pack(False, False, alpha, beta))
+        return out
 
     def symm(self, A, X, B=None, alpha=1.0, beta=0.0, absolute=False, out=None):
         """The product with every symmetric block itself, one launch per size class: block i of the stacked out <- beta b_i + alpha A_i x_i -

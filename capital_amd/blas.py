@@ -138,6 +138,50 @@ class engine:
         _lib.check(st, "blas::engine::_syrk_vbatched")
 
     @staticmethod
+    def _gemm_batched(matrixA, matrixB, matrixC, m, n, k, lda, stride_a, ldb, stride_b, ldc, stride_c, batch, srcPackage, stream=None):
+        """Every column-major m x n block C_i (matrixC + i stride_c, ld ldc) <- beta C_i + alpha op(A_i) op(B_i), m, n <= 256, any k, in one
+        launch (cap_dgemm_batched).  op(A_i) is m x k: AblasNoTrans - A_i is m x k (ld lda >= m) at matrixA + i stride_a, AblasTrans - k x m
+        (lda >= k); op(B_i) is k x n likewise.  alpha, beta and the two transposes come from the ArgPack_gemm.  beta == 0 does not read C;
+        alpha == 0 or k == 0 does not read A or B (they may be None).  C must not overlap A or B.  Asynchronous."""
+        _require_colmajor(srcPackage.order)
+        if m > 256 or n > 256:
+            raise _lib.CapitalError("_gemm_batched takes blocks of at most 256 rows and columns, got m = %d, n = %d" % (m, n))
+        st = _lib.lib().cap_dgemm_batched(int(srcPackage.transposeA), int(srcPackage.transposeB), m, n, k, srcPackage.alpha, dptr(matrixA), lda,
+                                          stride_a, dptr(matrixB), ldb, stride_b, srcPackage.beta, dptr(matrixC), ldc, stride_c, batch,
+                                          cur_stream(stream))
+        _lib.check(st, "blas::engine::_gemm_batched")
+
+    @staticmethod
+    def _gemm_vbatched_inner(plan, matrixX, matrixY, matrixG, m, n, ldx, ldy, ldg, stride_g, srcPackage, stream=None):
+        """On a cap_vbatch_plan: G_i (m x n at matrixG + i stride_g, ld ldg, batch order) <- beta G_i + alpha X_i^T Y_i, m, n <= 256, with
+        the stacked (sum n_i) x m matrixX and (sum n_i) x n matrixY of _potrs_vbatched: the contraction runs over the n_i rows of block i.
+        cap_dgemm_vbatched_inner, ONE launch whatever the size classes; an empty block gives beta G_i.  The transposes of the ArgPack_gemm
+        must be (AblasTrans, AblasNoTrans).  Asynchronous."""
+        _require_colmajor(srcPackage.order)
+        if (srcPackage.transposeA, srcPackage.transposeB) != (Transpose.AblasTrans, Transpose.AblasNoTrans):
+            raise _lib.CapitalError("_gemm_vbatched_inner computes X^T Y: the ArgPack_gemm must say (AblasTrans, AblasNoTrans)")
+        if m > 256 or n > 256:
+            raise _lib.CapitalError("_gemm_vbatched_inner takes outputs of at most 256 rows and columns, got m = %d, n = %d" % (m, n))
+        st = _lib.lib().cap_dgemm_vbatched_inner(plan, m, n, srcPackage.alpha, dptr(matrixX), ldx, dptr(matrixY), ldy, srcPackage.beta,
+                                                 dptr(matrixG), ldg, stride_g, cur_stream(stream))
+        _lib.check(st, "blas::engine::_gemm_vbatched_inner")
+
+    @staticmethod
+    def _gemm_vbatched_combine(plan, matrixV, matrixZ, matrixC, nrhs, k, ldv, ldz, stride_z, ldc, srcPackage, stream=None):
+        """On a cap_vbatch_plan: block i's rows of the stacked (sum n_i) x nrhs matrixC (ld ldc) <- beta C_i + alpha V_i Z_i, nrhs <= 256, any
+        k, with the stacked (sum n_i) x k matrixV of _cholupdate_vbatched and Z_i k x nrhs (ld ldz >= k) at matrixZ + i stride_z.
+        cap_dgemm_vbatched_combine, one launch per non-empty size class.  The transposes of the ArgPack_gemm must be (AblasNoTrans,
+        AblasNoTrans).  Asynchronous."""
+        _require_colmajor(srcPackage.order)
+        if (srcPackage.transposeA, srcPackage.transposeB) != (Transpose.AblasNoTrans, Transpose.AblasNoTrans):
+            raise _lib.CapitalError("_gemm_vbatched_combine computes V Z: the ArgPack_gemm must say (AblasNoTrans, AblasNoTrans)")
+        if nrhs > 256:
+            raise _lib.CapitalError("_gemm_vbatched_combine takes at most 256 columns, got nrhs = %d" % nrhs)
+        st = _lib.lib().cap_dgemm_vbatched_combine(plan, nrhs, k, srcPackage.alpha, dptr(matrixV), ldv, dptr(matrixZ), ldz, stride_z,
+                                                   srcPackage.beta, dptr(matrixC), ldc, cur_stream(stream))
+        _lib.check(st, "blas::engine::_gemm_vbatched_combine")
+
+    @staticmethod
     def _symm_batched(matrixA, matrixX, matrixB, matrixY, n, nrhs, lda, stride_a, ldx, stride_x, ldb, stride_b, ldy, stride_y, batch, srcPackage,
                       stream=None):
         """Y_i (n x nrhs, ld ldy, at matrixY + i stride_y) <- beta B_i + alpha A_i X_i with the SYMMETRIC n x n blocks A_i of which only the

@@ -481,6 +481,65 @@ int cap_dpoerr_batched(int uplo, int64_t n, int64_t nrhs, const double* A, int64
 int cap_dpoerr_vbatched(const cap_vbatch_plan* p, int uplo, int64_t nrhs, const double* A, const double* R, const double* B, int64_t ldb,
                         const double* X, int64_t ldx, const int* info, double* ferr, double* berr, int64_t lde, double* work, void* stream);
 
+/* Batched GENERAL products on the block layouts of the batched family (csrc/gemm_batched.hip): the level-3 product with two different
+ * operands - the right-hand side X^T y of the normal equations, B_1^T A^-1 B_2 = W_1^T W_2 from two cap_dtrsm_batched results, V_i^T x and
+ * V_i z of low-rank-plus-block operators.  For every block the column-major m x n block C_i (at C + i * stride_c, leading dimension ldc)
+ * becomes
+ *   beta C_i + alpha op(A_i) op(B_i),   0 <= m, n <= 256, any k >= 0 (the loop over k is inside the one launch, k is never split across
+ *   workgroups), fp64, one GPU - BLAS dgemm per block.
+ *   op(A_i) is m x k: transa = CAP_NOTRANS: A_i is m x k column-major at A + i * stride_a with lda >= m; CAP_TRANS: k x m with lda >= k.
+ *   op(B_i) is k x n: transb = CAP_NOTRANS: B_i is k x n with ldb >= k; CAP_TRANS: n x k with ldb >= n.
+ * Both transposes are layouts: the loader strides, nothing is copied.  A and B are never written.  The whole m x n rectangle of every C_i
+ * is written and nothing else: rows m .. ld - 1 of every column of C, A and B, the gaps between blocks and everything behind the last block
+ * are never addressed.
+ * The arithmetic, the same on every path: s_rc = sum_q a_rq b_qc on the fp64 16 x 16 x 4 MFMA from a ZERO accumulator with K ascending,
+ * four per instruction (rows >= m, columns >= n and k-positions >= k enter as +0.0 and are never addressed); then, without contraction,
+ *   t = alpha * s;   out = (beta == 0) ? t : fma(beta, c_old, t).
+ * beta == 0 never reads C: NaN and Inf there do not propagate.  alpha == 0 or k == 0 never addresses A or B, and they may be NULL.
+ * The contract is that of the batched entries above: ONE launch per fixed-size call on a 1-D grid (max(m, n) <= 64: a wavefront per 64 / NP
+ * blocks, NP the padded max(m, n); above: a workgroup of four waves per block), no `work` argument, no allocation, no memset, no atomics,
+ * no mutex, no helper stream, no host synchronisation, nothing between workgroups; asynchronous on `stream`; 64-bit offsets.  A large k
+ * with few blocks leaves most of the chip idle.
+ * cap_dgemm_vbatched_inner, on a cap_vbatch_plan: G_i (m x n at G + i * stride_g, leading dimension ldg, one output per block in BATCH
+ * order) becomes beta G_i + alpha X_i^T Y_i.  X is the STACKED (sum n_i) x m matrix and Y the stacked (sum n_i) x n matrix of
+ * cap_dpotrs_vbatched (ldx, ldy >= sum n_i); block i owns rows row_off[i] .. row_off[i] + n_i, the contraction length is n_i.  The output
+ * size does not depend on the block, so this is ONE launch whatever the plan's classes.  An EMPTY block (n_i = 0) is an empty sum:
+ * G_i <- beta G_i, that is alpha * (+0.0) for beta = 0 - deliberately unlike the other plan entries, which skip empty blocks: every G_i of
+ * the batch is defined after the call.
+ * cap_dgemm_vbatched_combine: C_i (n_i x nrhs, block i's rows of the stacked (sum n_i) x nrhs matrix C, ldc >= sum n_i) becomes
+ * beta C_i + alpha V_i Z_i.  V is the stacked (sum n_i) x k matrix of cap_dcholupdate_vbatched / cap_dsyrk_vbatched(CAP_NOTRANS)
+ * (ldv >= sum n_i), Z_i is k x nrhs column-major at Z + i * stride_z with ldz >= k, nrhs <= 256.  One launch per occurring size class, seven
+ * at most; empty blocks are neither read nor written.  The k x (sum n_i) layout of V is not offered.
+ * THE BIT CONTRACTS.
+ *   1. PLAN = FIXED: block i of cap_dgemm_vbatched_inner has the bits of cap_dgemm_batched(CAP_TRANS, CAP_NOTRANS, m, n, n_i, ..., batch = 1)
+ *      on its rows, block i of cap_dgemm_vbatched_combine those of cap_dgemm_batched(CAP_NOTRANS, CAP_NOTRANS, n_i, nrhs, k, ..., batch = 1),
+ *      whichever blocks share its wavefront or its class.
+ *   2. LAYOUT INDEPENDENCE: a block's bits are a function of (m, n, k, alpha, beta, its data) only - not of batch, index, any ld or
+ *      stride, or the alignment.
+ *   3. TRANS IS A LAYOUT: the same mathematical operands under any of the four (transa, transb) give the same bits.
+ *   4. ELEMENT INDEPENDENCE: c_rc equals the m = n = 1 product of row r of op(A) and column c of op(B), on the wave path and the
+ *      workgroup path alike: a column's bits do not depend on its company.
+ *   5. COMPOSITION: with B = A, cap_dgemm_batched(CAP_NOTRANS, CAP_TRANS) gives in its upper triangle the bits of
+ *      cap_dsyrk_batched(CAP_NOTRANS) with the same alpha, beta; with A the symmetrised full block, cap_dgemm_batched(CAP_NOTRANS,
+ *      CAP_NOTRANS) gives the bits of cap_dsymm_batched.
+ * Argument rules, in this order, all decided before any device call.  cap_dgemm_batched: a trans other than CAP_NOTRANS / CAP_TRANS; m, n,
+ * k or batch < 0; a NULL C with m n batch > 0; a NULL A or B with m n k batch > 0 and alpha != 0; ldc < m; lda or ldb below the operand's
+ * rows as stored; with batch > 1 a stride below ld x the stored columns; with alpha != 0 and k > 0 a C whose span overlaps A's or B's (as
+ * cap_dsymm_batched refuses Y) -> CAP_ERR_ARG; then m > 256 or n > 256 -> CAP_ERR_UNSUPPORTED; then a grid beyond one dimension (2^31 - 1
+ * workgroups) -> CAP_ERR_UNSUPPORTED; then m == 0, n == 0 or batch == 0 -> CAP_OK without a launch.
+ * The plan entries: a NULL plan; negative m / n / nrhs / k; NULL pointers when something would be launched (inner: G with m n batch > 0, X
+ * and Y with sum n_i > 0 and alpha != 0 besides; combine: C with nrhs > 0 and a non-empty block, V and Z with k > 0 and alpha != 0
+ * besides); a stacked leading dimension < sum n_i; ldg < m; with batch > 1 stride_g < ldg n; ldz < k; with batch > 1 stride_z < ldz nrhs
+ * -> CAP_ERR_ARG; then m, n or nrhs > 256 -> CAP_ERR_UNSUPPORTED; then nothing to launch -> CAP_OK; then a plan made without a device ->
+ * CAP_ERR_HIP.                                                                                                                          */
+int cap_dgemm_batched(int transa, int transb, int64_t m, int64_t n, int64_t k, double alpha, const double* A, int64_t lda, int64_t stride_a,
+                      const double* B, int64_t ldb, int64_t stride_b, double beta, double* C, int64_t ldc, int64_t stride_c, int64_t batch,
+                      void* stream);
+int cap_dgemm_vbatched_inner(const cap_vbatch_plan* p, int64_t m, int64_t n, double alpha, const double* X, int64_t ldx, const double* Y,
+                             int64_t ldy, double beta, double* G, int64_t ldg, int64_t stride_g, void* stream);
+int cap_dgemm_vbatched_combine(const cap_vbatch_plan* p, int64_t nrhs, int64_t k, double alpha, const double* V, int64_t ldv, const double* Z,
+                               int64_t ldz, int64_t stride_z, double beta, double* C, int64_t ldc, void* stream);
+
 /* Batched PIVOTED Cholesky factorization for symmetric positive SEMIdefinite blocks of up to 64 rows (csrc/pstrf_batched.hip): cap_dpstrf
  * on every block of a batch in ONE launch - numerical rank, a factor that survives zero pivots, the trace error of the low-rank
  * approximation - where cap_dpotrf_batched turns a block into NaN at the first pivot that is not > 0.  For every block
