@@ -24,6 +24,9 @@ gemm (and VarBatch.inner / VarBatch.combine): the GENERAL product with two diffe
 X^T y of normal equations, cross terms W_1^T W_2 of two trsm results, V_i^T x and V_i z of low-rank-plus-block operators - one launch
 (cap_dgemm_batched / cap_dgemm_vbatched_inner, one launch for any plan / cap_dgemm_vbatched_combine, one per size class,
 csrc/gemm_batched.hip).
+blocktri_potrf / blocktri_potrs: blocks LINKED to each other - many independent block-tridiagonal SPD chains (Kalman / RTS smoothers, Gauss-Markov
+random fields, splines), T diagonal blocks of n <= 64 rows each, factored and solved in one launch per call with the chain walked
+inside the kernel (cap_dpotrf_blocktri_batched / cap_dpotrs_blocktri_batched, csrc/blocktri_batched.hip).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
@@ -52,6 +55,9 @@ _PACK_VC = lapack.ArgPack_pocon_vbatched(lapack.Order.AlapackColumnMajor, lapack
 _PACK_VE = lapack.ArgPack_poerr_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_P = lapack.ArgPack_pstrf_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_VP = lapack.ArgPack_pstrf_vbatched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_BF = lapack.ArgPack_potrf_blocktri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
+_PACK_BS = {h: lapack.ArgPack_potrs_blocktri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper, half=v)
+            for h, v in ((None, 0), ("forward", 1), ("backward", 2))}
 
 
 def _check(t, name, dims):
@@ -314,6 +320,96 @@ def schur(R, B, C, info=None):
     stream."""
     trsm(R, B, trans=True, info=info)
     return syrk(B, C, trans=True, alpha=-1.0, beta=1.0)
+
+
+def _chain_blocks(t, name, batch=None, blocks=None, n=None):
+    """(batch, blocks, n, ld, step, stride) of a (batch, blocks, n, n) tensor whose t[c, i] is read as column-major memory with ld = stride(2)"""
+    _check(t, name, (4,))
+    b, k, r, c = t.shape
+    if r != c or (batch is not None and (b, k, r) != (batch, blocks, n)):
+        raise _lib.CapitalError("%s must be (batch, %s, n, n)%s, got shape %s"
+                                % (name, "T" if batch is None else "T - 1", "" if batch is None else " = (%d, %d, %d, %d)" % (batch, blocks, n, n),
+                                   tuple(t.shape)))
+    if t.numel() == 0:
+        return b, k, r, max(r, 1), max(r * r, 1), max(k * r * r, 1)
+    if r > 1 and t.stride(3) != 1:
+        raise _lib.CapitalError("%s must have stride(-1) == 1, got strides %s" % (name, t.stride()))
+    ld = t.stride(2) if r > 1 else max(t.stride(2), 1)
+    step, stride = t.stride(1), t.stride(0)
+    if ld < r or (k > 1 and step < ld * r) or (b > 1 and stride < (step * k if k > 1 else ld * r)):
+        raise _lib.CapitalError("%s: blocks overlap (strides %s)" % (name, t.stride()))
+    return b, k, r, ld, max(step, 0), max(stride, 0)
+
+
+def _chain(D, E):
+    batch, T, n, ldd, step_d, stride_d = _chain_blocks(D, "D")
+    if n > 64:
+        raise _lib.CapitalError("block-tridiagonal Cholesky takes blocks of at most 64 rows, got n = %d" % n)
+    if E is None:
+        if T > 1:
+            raise _lib.CapitalError("E may be None only when T == 1, got T = %d" % T)
+        return batch, T, n, ldd, step_d, stride_d, n, n * n, n * n
+    if T < 1:
+        raise _lib.CapitalError("D must hold at least one block per chain")
+    _, _, _, lde, step_e, stride_e = _chain_blocks(E, "E", batch, T - 1, n)
+    if E.device != D.device:
+        raise _lib.CapitalError("D and E live on different devices")
+    (a0, a1), (b0, b1) = _span(D), _span(E)
+    if a0 < b1 and b0 < a1:
+        raise _lib.CapitalError("D and E overlap")
+    return batch, T, n, ldd, step_d, stride_d, lde, step_e, stride_e
+
+
+def blocktri_potrf(D, E, logdet=False):
+    """Cholesky factors of a batch of block-tridiagonal SPD chains, in place, in ONE launch - the recurrence of a Kalman / RTS smoother, a
+    Gauss-Markov random field or a spline system run inside the kernel instead of 3 launches per chain position.
+    D: fp64 device tensor (batch, T, n, n), the diagonal blocks, n <= 64; E: (batch, T - 1, n, n), E[c, i] = A_c[block i + 1, block i] in
+    torch's reading, or None when T == 1.  Both need stride(-1) == 1; stride(-2) >= n and the other strides are free as long as no two
+    blocks overlap.  In torch's row-major reading the factor is L, block lower bidiagonal, with A = L L^T: L_ii replaces the LOWER triangle
+    of D[c, i] (what torch reads as the strictly upper triangle is neither read nor written, exactly as in potrf) and L_(i+1, i) replaces
+    E[c, i] - together they equal torch.linalg.cholesky of the assembled (T n) x (T n) matrix.
+    Returns info (int32, batch entries: 0, or the 1-based row of the T n system of the first pivot that is not > 0 - from there on the
+    chain holds NaN), or (info, logdet) with logdet=True: log det A_c, NaN for a failed chain.
+    A chain's bits are those of the host-driven loop potrf(D[:, i]); trsm(D[:, i], E[:, i], info=.); syrk(E[:, i], D[:, i + 1], trans=True,
+    alpha=-1, beta=1) and depend on (n, T, its data) alone.  Asynchronous on the current stream; nothing is read back."""
+    batch, T, n, ldd, step_d, stride_d, lde, step_e, stride_e = _chain(D, E)
+    info, ld = lapack.engine._potrf_blocktri_batched(D, E, n, T, ldd, step_d, stride_d, lde, step_e, stride_e, batch, _PACK_BF,
+                                                     want_logdet=bool(logdet))
+    return (info, ld) if logdet else info
+
+
+def blocktri_potrs(D, E, B, info=None, half=None):
+    """Solves A_c x = b in place with the factors blocktri_potrf left in D and E (same layout rules), in ONE launch.  B: fp64 device tensor
+    (batch, nrhs, T n) or (batch, T n), every right-hand side contiguous (stride(-1) == 1), with potrs's rules; it is overwritten.
+    half: None - both sweeps (the solution); "forward" - L^-1 b alone (whitening, the terms of a state-space log-likelihood); "backward" -
+    L^-T z alone (a sample of the Gauss-Markov field with precision A from z ~ N(0, I)), L the block lower bidiagonal factor of torch's
+    reading: L_ii in the lower triangle of D[c, i], L_(i+1, i) in E[c, i], L = torch.linalg.cholesky of the assembled matrix.  "forward"
+    followed by "backward" leaves the bits of the full solve.  info: what blocktri_potrf returned, or None - a chain with info != 0 gets NaN.
+    Returns B.  Asynchronous on the current stream."""
+    if half not in _PACK_BS:
+        raise _lib.CapitalError("half must be None, 'forward' or 'backward', got %r" % (half,))
+    batch, T, n, ldd, step_d, stride_d, lde, step_e, stride_e = _chain(D, E)
+    _check(B, "B", (2, 3))
+    B3 = B.unsqueeze(1) if B.dim() == 2 else B
+    if B3.shape[0] != batch or B3.shape[2] != T * n:
+        raise _lib.CapitalError("B must be (batch, nrhs, T n) or (batch, T n) with batch = %d, T n = %d, got shape %s" % (batch, T * n, tuple(B.shape)))
+    nrhs = B3.shape[1]
+    if T * n > 1 and B3.stride(2) != 1:
+        raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
+    ldb = B3.stride(1) if nrhs > 1 else max(T * n, 1)
+    stride_b = B3.stride(0)
+    if ldb < T * n or (batch > 1 and stride_b < ldb * nrhs):
+        raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
+    if B.device != D.device:
+        raise _lib.CapitalError("D and B live on different devices")
+    for t, name in ((D, "D"), (E, "E")):
+        if t is not None:
+            (a0, a1), (b0, b1) = _span(t), _span(B)
+            if a0 < b1 and b0 < a1:
+                raise _lib.CapitalError("%s and B overlap" % name)
+    lapack.engine._potrs_blocktri_batched(D, E, B3, n, T, nrhs, ldd, step_d, stride_d, lde, step_e, stride_e, ldb, max(stride_b, 0), batch,
+                                          _info(info, D), _PACK_BS[half])
+    return B
 
 
 def _gemm_pack(transa, transb, alpha, beta):

@@ -1,0 +1,163 @@
+// The address arithmetic of blocktri_batched.hip: which element of D, E, B, info / logdet and of the two LDS areas a lane touches at a
+// chain position, and whether it touches it at all - as functions the kernels call AND a plain C++ program can call
+// (tests/test_blocktri_addr.py replays the kernels' loops on the CPU, lane by lane, over the rows of tests/blocktri_cases.py: every
+// addressed offset inside its block, no E block and no successor at position T - 1, no E at all with T = 1, nothing from a dead lane
+// group, the written set exactly the triangles, the E blocks and the right-hand-side segments).  The kernels form no address any other way.
+// Nothing here knows a pointer: a global offset is in elements from the operand's base pointer (D, E, B, info, logdet), an LDS offset in
+// doubles from the start of the area.
+//
+// THE SHAPES.  A wavefront carries G = 64 / NP chains in lane groups of NP lanes (NP = 8 / 16 / 32 / 64, the smallest >= n): lane l belongs
+// to chain wg G + l / NP and is lane l % NP of its group.  Three ways of looking at a block occur:
+//   triangle   potrf_batched.hip's: lane r of a group walks row r of the upper triangle, a loop runs over the columns (a column is contiguous);
+//   column     trsm_batched.hip's: lane k of a group owns column k (of E: a column of W; of B: right-hand side pass NP + k), rows in registers;
+//   tile       syrk_batched.hip's / gemm_batched.hip's: the 64 wave rows (and columns) w = 16 s + l % 16 are row w % NP of chain w / NP, lane l
+//              supplies k position q + l / 16 of slab s and holds in accumulator register r of tile (si, sj) wave row 16 si + l % 16, wave
+//              column 16 sj + l / 16 + 4 r; a tile exists where both slabs belong to the same chain.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define BT_HD __host__ __device__ __forceinline__
+#else
+#define BT_HD inline
+#endif
+
+constexpr int BT_MAX = 64;             // largest block
+constexpr int BT_LDX = 68;             // doubles per line of the exchange area (64 wave columns + 4: the four k positions of a slab start 4 banks apart)
+
+struct BtAt {                          // one access: the offset and whether the lane makes it
+  int64_t off;
+  bool on;
+};
+
+struct BtGeo {                         // one operand of one launch: blocks of n x n, leading dimension ld, `step` apart along a chain, chains `stride` apart
+  int64_t ld, step, stride;
+  int64_t T, batch;                    // positions of a chain (the operand holds T blocks for D, T - 1 for E), chains
+  int n, NP;
+};
+
+BT_HD constexpr int bt_padded(const int n) { return n <= 8 ? 8 : n <= 16 ? 16 : n <= 32 ? 32 : 64; }
+BT_HD constexpr int bt_group(const int NP, const int w) { return w / NP; }          // lane or wave row / column -> its lane group
+BT_HD constexpr int bt_idx(const int NP, const int w) { return w % NP; }            //                           -> its index there
+BT_HD constexpr int64_t bt_chain(const int NP, const int64_t wg, const int w) { return wg * (64 / NP) + bt_group(NP, w); }
+BT_HD constexpr bool bt_live(const BtGeo& g, const int64_t wg, const int w) { return bt_chain(g.NP, wg, w) < g.batch; }
+BT_HD constexpr bool bt_has_next(const int64_t T, const int64_t pos) { return pos + 1 < T; }   // position pos has a coupling block and a successor
+BT_HD constexpr int64_t bt_block(const BtGeo& g, const int64_t chain, const int64_t pos) { return chain * g.stride + pos * g.step; }
+
+// does tile (si, sj) exist: both slabs carry the same chain(s); upper: only the tiles of the upper triangle (the factor's successor update)
+BT_HD constexpr bool bt_tile(const int NP, const int si, const int sj, const bool upper) {
+  return (si * 16) / NP == (sj * 16) / NP && (!upper || si <= sj);
+}
+// wave-uniform: does slab s hold a row below n
+BT_HD constexpr bool bt_slab_on(const int NP, const int s, const int n) { return (s * 16) % NP < n; }
+
+// ------------------------------------------------------------------------------------------------ D
+// TRIANGLE of diagonal block `pos`: lane -> row, column c (the first load of a chain, the store of every factor, the solve's load of U)
+BT_HD BtAt bt_tri_at(const BtGeo& g, const int64_t wg, const int lane, const int64_t pos, const int c) {
+  const int r = bt_idx(g.NP, lane);
+  BtAt a;
+  a.on = bt_live(g, wg, lane) && pos >= 0 && pos < g.T && r <= c && c < g.n;
+  a.off = bt_block(g, bt_chain(g.NP, wg, lane), pos) + r + (int64_t)c * g.ld;
+  return a;
+}
+
+// TILE of the SUCCESSOR block pos + 1 (the factor reads D_(pos+1) where the rank-n product lands): register r of tile (si, sj)
+BT_HD BtAt bt_next_at(const BtGeo& g, const int64_t wg, const int lane, const int64_t pos, const int si, const int sj, const int r) {
+  const int lr = lane & 15, kg = lane >> 4;
+  const int wi = si * 16 + lr, wj = sj * 16 + kg + 4 * r;
+  const int row = bt_idx(g.NP, wi), col = bt_idx(g.NP, wj);
+  BtAt a;
+  a.on = bt_group(g.NP, wi) == bt_group(g.NP, wj) && row <= col && col < g.n && bt_live(g, wg, wi) && pos >= 0 && bt_has_next(g.T, pos);
+  a.off = bt_block(g, bt_chain(g.NP, wg, wi), pos + 1) + row + (int64_t)col * g.ld;
+  return a;
+}
+
+// ------------------------------------------------------------------------------------------------ E (g.T is the chain's T: E holds T - 1 blocks)
+// COLUMN of coupling block `pos` (the factor: W replaces B column by column): lane -> column, row q
+BT_HD BtAt bt_ecol_at(const BtGeo& g, const int64_t wg, const int lane, const int64_t pos, const int q) {
+  const int c = bt_idx(g.NP, lane);
+  BtAt a;
+  a.on = bt_live(g, wg, lane) && pos >= 0 && bt_has_next(g.T, pos) && c < g.n && q >= 0 && q < g.n;
+  a.off = bt_block(g, bt_chain(g.NP, wg, lane), pos) + q + (int64_t)c * g.ld;
+  return a;
+}
+
+// SLAB of coupling block `pos` as an MFMA operand of the solve: slab s, k step q (a multiple of four).  trans: the lane supplies
+// W^T(row, k) = W[k, row] (forward sweep), else W(row, k) (backward sweep)
+BT_HD BtAt bt_eslab_at(const BtGeo& g, const int64_t wg, const int lane, const int64_t pos, const int s, const int q, const bool trans) {
+  const int lr = lane & 15, kg = lane >> 4;
+  const int w = s * 16 + lr, row = bt_idx(g.NP, w), k = q + kg;
+  BtAt a;
+  a.on = bt_live(g, wg, w) && pos >= 0 && bt_has_next(g.T, pos) && row < g.n && k < g.n;
+  a.off = bt_block(g, bt_chain(g.NP, wg, w), pos) + (trans ? k + (int64_t)row * g.ld : row + (int64_t)k * g.ld);
+  return a;
+}
+
+// ------------------------------------------------------------------------------------------------ B, info, logdet
+// COLUMN of segment `pos` of the right-hand sides: lane -> right-hand side pass NP + lane % NP, row r of the segment (row pos n + r of the system)
+BT_HD BtAt bt_rhs_at(const BtGeo& g, const int64_t ldb, const int64_t stride_b, const int64_t nrhs, const int64_t wg, const int lane, const int64_t pass,
+                     const int64_t pos, const int r) {
+  const int64_t col = pass * g.NP + bt_idx(g.NP, lane);
+  BtAt a;
+  a.on = bt_live(g, wg, lane) && col < nrhs && pos >= 0 && pos < g.T && r >= 0 && r < g.n;
+  a.off = bt_chain(g.NP, wg, lane) * stride_b + col * ldb + pos * g.n + r;
+  return a;
+}
+BT_HD constexpr int64_t bt_rhs_passes(const int NP, const int64_t nrhs) { return (nrhs + NP - 1) / NP; }
+
+// the chain's entry of info and logdet: lane 0 of a live group
+BT_HD BtAt bt_scalar_at(const BtGeo& g, const int64_t wg, const int lane) {
+  BtAt a;
+  a.on = bt_live(g, wg, lane) && bt_idx(g.NP, lane) == 0;
+  a.off = bt_chain(g.NP, wg, lane);
+  return a;
+}
+// every lane of a live group reads its chain's info in the solve
+BT_HD BtAt bt_info_at(const BtGeo& g, const int64_t wg, const int lane) {
+  BtAt a;
+  a.on = bt_live(g, wg, lane);
+  a.off = bt_chain(g.NP, wg, lane);
+  return a;
+}
+
+// ------------------------------------------------------------------------------------------------ LDS
+// the factor image of a group (batched_small.h's PbImg<NP>::at, restated for the sweep; the kernels assert that the two agree)
+BT_HD constexpr int bt_img_ld(const int NP) { return NP + 2; }
+BT_HD constexpr int bt_img_size(const int NP) { return (NP / 2) * bt_img_ld(NP); }
+BT_HD constexpr int bt_img_at(const int NP, const int r, const int c) {
+  return r < NP / 2 ? r * bt_img_ld(NP) + (c - r) : (NP - 1 - r) * bt_img_ld(NP) + c + 1;
+}
+BT_HD constexpr int bt_img_base(const int NP, const int lane) { return bt_group(NP, lane) * bt_img_size(NP); }
+
+// the 64 logarithms of the wavefront's diagonals: entry j of the lane's group
+BT_HD constexpr int bt_log_at(const int NP, const int lane, const int j) { return bt_group(NP, lane) * NP + j; }
+
+// the exchange area of the wavefront: NP lines of BT_LDX doubles; line q holds row q of the 64 columns the lanes own
+BT_HD constexpr int bt_x_size(const int NP) { return NP * BT_LDX; }
+BT_HD constexpr int bt_x_own(const int q, const int lane) { return q * BT_LDX + lane; }          // the lane's own column, row q
+// as an MFMA operand: slab s, k step q: the lane supplies (k = q + lane / 16, wave column 16 s + lane % 16); off below k < n
+BT_HD BtAt bt_x_slab(const int n, const int lane, const int s, const int q) {
+  const int k = q + (lane >> 4);
+  BtAt a;
+  a.on = k < n;
+  a.off = k * BT_LDX + s * 16 + (lane & 15);
+  return a;
+}
+// the solve's product, register r of tile (si, sj), goes to row `row` of the column of the lane that owns wave column wj
+BT_HD BtAt bt_x_tile(const int n, const int NP, const int lane, const int si, const int sj, const int r) {
+  const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
+  BtAt a;
+  a.on = bt_group(NP, wi) == bt_group(NP, wj) && bt_idx(NP, wi) < n;
+  a.off = bt_idx(NP, wi) * BT_LDX + wj;
+  return a;
+}
+// the factor's successor, register r of tile (si, sj): element (row, col) of the image of the group of wave row wi; on exactly where
+// bt_next_at is, for a live group with a successor
+BT_HD BtAt bt_img_tile(const int n, const int NP, const int lane, const int si, const int sj, const int r) {
+  const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
+  const int row = bt_idx(NP, wi), col = bt_idx(NP, wj);
+  BtAt a;
+  a.on = bt_group(NP, wi) == bt_group(NP, wj) && row <= col && col < n;
+  a.off = bt_img_base(NP, wi) + bt_img_at(NP, row, col);
+  return a;
+}

@@ -69,6 +69,8 @@ class Method(enum.IntEnum):
     AlapackPoerrVbatched = 0x1D        # extension: not in the reference's enum
     AlapackPstrfBatched = 0x1E         # extension: not in the reference's enum
     AlapackPstrfVbatched = 0x1F        # extension: not in the reference's enum
+    AlapackPotrfBlocktriBatched = 0x20 # extension: not in the reference's enum
+    AlapackPotrsBlocktriBatched = 0x21 # extension: not in the reference's enum
 
 
 class ArgPack_potrf:
@@ -245,6 +247,18 @@ class ArgPack_pstrf_vbatched:
         self.order, self.uplo = Order(order), UpLo(uplo)
 
 
+class ArgPack_potrf_blocktri_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotrfBlocktriBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
+
+
+class ArgPack_potrs_blocktri_batched:
+    def __init__(self, order, uplo, half=0):
+        self.method = Method.AlapackPotrsBlocktriBatched
+        self.order, self.uplo, self.half = Order(order), UpLo(uplo), int(half)      # half: 0 both sweeps, 1 forward only, 2 backward only
+
+
 BATCHED_SMALL_MAX = 64      # cap_dpotrf_batched / cap_dpotrs_batched: a wavefront per block
 BATCHED_MAX = 256           # cap_dpotrf_batched_blocked / cap_dpotrs_batched_blocked: a workgroup per block
 
@@ -403,6 +417,42 @@ class engine:
         st = fn(int(srcPackage.uplo), n, nrhs, dptr(matrixR), ldr, stride_r, dptr(matrixB), ldb, stride_b, batch,
                 info.data_ptr() if info is not None else None, cur_stream(stream))
         _lib.check(st, "lapack::engine::_potrs_batched")
+
+    @staticmethod
+    def _potrf_blocktri_batched(matrixD, matrixE, n, T, ldd, step_d, stride_d, lde, step_e, stride_e, batch, srcPackage, want_logdet=False, stream=None):
+        """`batch` block-tridiagonal SPD chains of T diagonal blocks of n x n, n <= 64, <- their block bidiagonal Cholesky factors, in place, in
+        one launch (cap_dpotrf_blocktri_batched): block (c, i) of D is column-major with ld ldd at matrixD + c stride_d + i step_d, E likewise
+        with T - 1 blocks per chain (matrixE may be None when T <= 1).  U_i replaces the upper triangle of D_i, W_i = U_i^-T A[i, i + 1]
+        replaces E_i.  Returns (info, logdet): an int32 device tensor of batch entries (0, or the 1-based row of the T n system of the first
+        pivot that is not > 0) and, with want_logdet, an fp64 one with log det A_c (NaN for a failed chain), else None.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        if n > BATCHED_SMALL_MAX:
+            raise _lib.CapitalError("block-tridiagonal Cholesky: blocks of n = %d rows exceed the limit of %d rows per block" % (n, BATCHED_SMALL_MAX))
+        L = _lib.lib()
+        dev = matrixD.device if isinstance(matrixD, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        info = torch.zeros(max(batch, 1), dtype=torch.int32, device=dev)
+        logdet = torch.zeros(max(batch, 1), dtype=torch.float64, device=dev) if want_logdet else None
+        st = L.cap_dpotrf_blocktri_batched(int(srcPackage.uplo), n, T, dptr(matrixD), ldd, step_d, stride_d, dptr(matrixE), lde, step_e, stride_e,
+                                           info.data_ptr(), logdet.data_ptr() if want_logdet else None, batch, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrf_blocktri_batched")
+        return info[:max(batch, 0)], (logdet[:max(batch, 0)] if want_logdet else None)
+
+    @staticmethod
+    def _potrs_blocktri_batched(matrixD, matrixE, matrixB, n, T, nrhs, ldd, step_d, stride_d, lde, step_e, stride_e, ldb, stride_b, batch, info,
+                                srcPackage, stream=None):
+        """B_c ((T n) x nrhs, ld ldb, at matrixB + c stride_b) <- A_c^-1 B_c with the factors _potrf_blocktri_batched left in matrixD and
+        matrixE, n <= 64, in one launch (cap_dpotrs_blocktri_batched).  srcPackage.half = 1: the forward sweep alone (R^-T B), 2: the backward
+        sweep alone (R^-1 B).  info: what _potrf_blocktri_batched returned, or None; a chain with info != 0 gets NaN.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        if n > BATCHED_SMALL_MAX:
+            raise _lib.CapitalError("block-tridiagonal Cholesky: blocks of n = %d rows exceed the limit of %d rows per block" % (n, BATCHED_SMALL_MAX))
+        L = _lib.lib()
+        st = L.cap_dpotrs_blocktri_batched(int(srcPackage.uplo), int(srcPackage.half), n, T, nrhs, dptr(matrixD), ldd, step_d, stride_d, dptr(matrixE),
+                                           lde, step_e, stride_e, dptr(matrixB), ldb, stride_b, engine._batched_info(info, batch), batch,
+                                           cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrs_blocktri_batched")
 
     @staticmethod
     def _batched_info(info, batch):

@@ -540,6 +540,53 @@ int cap_dgemm_vbatched_inner(const cap_vbatch_plan* p, int64_t m, int64_t n, dou
 int cap_dgemm_vbatched_combine(const cap_vbatch_plan* p, int64_t nrhs, int64_t k, double alpha, const double* V, int64_t ldv, const double* Z,
                                int64_t ldz, int64_t stride_z, double beta, double* C, int64_t ldc, void* stream);
 
+/* Batched BLOCK-TRIDIAGONAL Cholesky factor and solve (csrc/blocktri_batched.hip): the first operation of the batched family that links
+ * blocks to each other - Kalman / RTS smoothers and state-space likelihoods, Gauss-Markov random fields, splines, line-implicit solvers.
+ * `batch` independent chains; chain c is the symmetric positive definite block-tridiagonal matrix A_c of T n rows, 1 <= n <= 64, T >= 1,
+ * with diagonal blocks D_(c,0) .. D_(c,T-1) and the coupling blocks A_c[block i, block i + 1] = B_(c,i), i = 0 .. T - 2, fp64, one GPU.
+ * Block (c, i) of D is the column-major n x n block at D + c * stride_d + i * step_d with leading dimension ldd; only its UPPER triangle
+ * is read and written.  E is addressed likewise (lde, step_e, stride_e) and holds T - 1 full n x n blocks per chain: E_(c,i) = B_(c,i).
+ * cap_dpotrf_blocktri_batched, in place:
+ *   S_0 = D_0;   U_i = chol(S_i), U_i^T U_i = S_i, upper, in the upper triangle of D_i;   W_i = U_i^-T B_i in E_i;
+ *   S_(i+1) = D_(i+1) - W_i^T W_i.
+ * A_c = R^T R with R block upper bidiagonal (U_i on its diagonal, W_i to the right of U_i).  Read ROW-major the same memory holds the
+ * block lower bidiagonal L = R^T with A = L L^T: L_ii in the lower triangle of D[c][i], L_(i+1,i) in E[c][i].
+ * info[c] (required) is 0 or the 1-based row of the T n system of the first pivot that is not > 0: i n + the row cap_dpotrf_batched
+ * reports for S_i.  logdet may be NULL; logdet[c] = s after s = 0; s += ld_i for i ascending, ld_i what cap_dpotrf_batched returns for S_i
+ * (NaN for a failed chain).
+ * cap_dpotrs_blocktri_batched: B is the column-major (T n) x nrhs right-hand side of chain c at B + c * stride_b (ldb >= T n), any nrhs
+ * (more than NP right-hand sides are further passes inside the launch).  half = 0: A x = b (both sweeps); 1: the forward sweep alone,
+ * R^-T b (whitening, log-likelihood terms); 2: the backward sweep alone, R^-1 z (sampling a field with precision A).  info may be NULL;
+ * a chain with info[c] != 0 gets NaN.  D and E are not written.
+ * THE BIT CONTRACT IS A COMPOSITION: a chain's D, E, info, logdet and solutions are, bit for bit, what the fixed-size entries give when the
+ * host drives the recurrence on that chain's blocks.  Factor, i ascending: cap_dpotrf_batched on block i; cap_dtrsm_batched(CAP_TRANS)
+ * with that factor and its info on the n columns of E_i; cap_dsyrk_batched(CAP_TRANS, alpha = -1, beta = 1) of E_i into the upper triangle
+ * of D_(i+1) (every element its own chain on the fp64 16 x 16 x 4 MFMA from a zero accumulator, K ascending, then t = alpha s,
+ * fma(beta, d, t), uncontracted).  Forward sweep, i ascending: cap_dtrsm_batched(CAP_TRANS) on segment i, then cap_dgemm_batched(CAP_TRANS,
+ * CAP_NOTRANS, alpha = -1, beta = 1) of E_i and segment i into segment i + 1.  Backward sweep, i descending: cap_dgemm_batched(CAP_NOTRANS,
+ * CAP_NOTRANS, -1, 1) of E_i and segment i + 1 into segment i, then cap_dtrsm_batched(CAP_NOTRANS).  half = 1 followed by half = 2 has
+ * the bits of half = 0.  CONSEQUENCES: a chain's bits depend on (n, T, its data) alone - not on batch, the chain's index, any leading
+ * dimension, step or stride, the alignment, the chains that share its wavefront or the columns that travel with a column.  After a
+ * failure at position i, D_i holds what cap_dpotrf_batched leaves, E_i .. E_(T-2) and the upper triangles of D_(i+1) .. D_(T-1) hold NaN,
+ * the chain's solutions are NaN and no other chain is affected.
+ * The contract is that of the batched entries above: ONE launch per call on a 1-D grid - a wavefront carries 64 / NP chains (NP = 8, 16,
+ * 32 or 64 >= n) and walks their positions in a loop inside the kernel - no `work` argument, no scratch, no allocation, no memset, no
+ * atomics, no mutex, no helper stream, nothing between workgroups; asynchronous on `stream`; 64-bit offsets.  A chain is sequential in
+ * its wavefront: a few long chains leave most of the chip idle.  Position T - 1 addresses no coupling block and no successor, T = 1
+ * addresses no E at all (E may then be NULL).  Pad rows, the strictly lower triangles of D, the gaps between blocks and chains and
+ * everything behind the last block are never addressed.
+ * Argument rules, in this order, all decided before any device call: 1. n, T, nrhs or batch < 0 -> CAP_ERR_ARG; 2. with n T batch (solve:
+ * and nrhs) > 0 a NULL D, a NULL info (factor) or B (solve), a NULL E with T > 1 -> CAP_ERR_ARG; 3. ldd or lde (T > 1) < n, with more than
+ * one block per chain a step < ld n, with batch > 1 a stride < step x the blocks of a chain (T for D, T - 1 for E; ld n where that is one
+ * block), ldb < T n, with batch > 1 stride_b < ldb nrhs, all in 128-bit arithmetic -> CAP_ERR_ARG; 4. half outside 0 .. 2 -> CAP_ERR_ARG;
+ * 5. uplo = CAP_LOWER -> CAP_ERR_UNSUPPORTED; 6. n > 64 -> CAP_ERR_UNSUPPORTED; 7. T n > 2^31 - 1 -> CAP_ERR_UNSUPPORTED; 8. a grid beyond
+ * one dimension (2^31 - 1 workgroups) -> CAP_ERR_UNSUPPORTED; 9. nothing to do (n, T, batch or nrhs = 0) -> CAP_OK, nothing touched.        */
+int cap_dpotrf_blocktri_batched(int uplo, int64_t n, int64_t T, double* D, int64_t ldd, int64_t step_d, int64_t stride_d, double* E, int64_t lde,
+                                int64_t step_e, int64_t stride_e, int* info, double* logdet, int64_t batch, void* stream);
+int cap_dpotrs_blocktri_batched(int uplo, int half, int64_t n, int64_t T, int64_t nrhs, const double* D, int64_t ldd, int64_t step_d,
+                                int64_t stride_d, const double* E, int64_t lde, int64_t step_e, int64_t stride_e, double* B, int64_t ldb,
+                                int64_t stride_b, const int* info, int64_t batch, void* stream);
+
 /* Batched PIVOTED Cholesky factorization for symmetric positive SEMIdefinite blocks of up to 64 rows (csrc/pstrf_batched.hip): cap_dpstrf
  * on every block of a batch in ONE launch - numerical rank, a factor that survives zero pivots, the trace error of the low-rank
  * approximation - where cap_dpotrf_batched turns a block into NaN at the first pivot that is not > 0.  For every block
