@@ -57,6 +57,7 @@ SIGNATURES = {
     "cap_dgemm_vbatched_combine": (cint, [ptr, i64, i64, dbl, ptr, i64, ptr, i64, i64, dbl, ptr, i64, ptr]),
     "cap_dpotrf_blocktri_batched": (cint, [cint, i64, i64, ptr, i64, i64, i64, ptr, i64, i64, i64, ptr, ptr, i64, ptr]),
     "cap_dpotrs_blocktri_batched": (cint, [cint, cint, i64, i64, i64, ptr, i64, i64, i64, ptr, i64, i64, i64, ptr, i64, i64, ptr, i64, ptr]),
+    "cap_dpotri_blocktri_batched": (cint, [cint, cint, i64, i64, ptr, i64, i64, i64, ptr, i64, i64, i64, ptr, i64, ptr]),
     "cap_dsymm_batched": (cint, [cint, cint, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, i64, ptr]),
     "cap_dsymm_vbatched": (cint, [ptr, cint, cint, i64, dbl, ptr, ptr, i64, dbl, ptr, i64, ptr, i64, ptr]),
     "cap_dlansy_batched": (cint, [cint, cint, i64, ptr, i64, i64, i64, ptr, ptr]),

@@ -27,6 +27,8 @@ csrc/gemm_batched.hip).
 blocktri_potrf / blocktri_potrs: blocks LINKED to each other - many independent block-tridiagonal SPD chains (Kalman / RTS smoothers, Gauss-Markov
 random fields, splines), T diagonal blocks of n <= 64 rows each, factored and solved in one launch per call with the chain walked
 inside the kernel (cap_dpotrf_blocktri_batched / cap_dpotrs_blocktri_batched, csrc/blocktri_batched.hip).
+blocktri_potri: the MARGINAL COVARIANCES of those chains from the factor - the diagonal blocks and the lag-one blocks of the inverse, the
+smoother's other half - in one launch, without the (T n) x (T n) inverse (cap_dpotri_blocktri_batched, csrc/blocktri_potri_batched.hip).
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
@@ -58,6 +60,7 @@ _PACK_VP = lapack.ArgPack_pstrf_vbatched(lapack.Order.AlapackColumnMajor, lapack
 _PACK_BF = lapack.ArgPack_potrf_blocktri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 _PACK_BS = {h: lapack.ArgPack_potrs_blocktri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper, half=v)
             for h, v in ((None, 0), ("forward", 1), ("backward", 2))}
+_PACK_BI = lapack.ArgPack_potri_blocktri_batched(lapack.Order.AlapackColumnMajor, lapack.UpLo.AlapackUpper)
 
 
 def _check(t, name, dims):
@@ -410,6 +413,25 @@ def blocktri_potrs(D, E, B, info=None, half=None):
     lapack.engine._potrs_blocktri_batched(D, E, B3, n, T, nrhs, ldd, step_d, stride_d, lde, step_e, stride_e, ldb, max(stride_b, 0), batch,
                                           _info(info, D), _PACK_BS[half])
     return B
+
+
+def blocktri_potri(D, E, info=None, symmetric=False):
+    """The marginal covariances of a batch of block-tridiagonal SPD chains from the factors blocktri_potrf left in D and E (same layout
+    rules), in place, in ONE launch: the diagonal blocks and the lag-one blocks of Sigma = A_c^-1 - what a Kalman / RTS smoother or a
+    Gauss-Markov field fit needs beside the mean - by a backward recurrence on the factor, without the (T n) x (T n) inverse.
+    In torch's row-major reading afterwards: the LOWER triangle of D[c, i] holds Sigma[block i, block i] and E[c, i] holds
+    Sigma[block i + 1, block i] (the convention by which E[c, i] = A[block i + 1, block i] on input) - together the block-tridiagonal part
+    of torch.linalg.inv of the assembled matrix.  What torch reads as the strictly upper triangle of D[c, i] is neither read nor written,
+    unless symmetric=True (the C ABI's fill = 1): then it becomes the bit-identical mirror, copied and never computed a second time.
+    The factor is overwritten: clone D and E first if blocktri_potrs is still to be called.  A zero on a diagonal is not detected.
+    info: what blocktri_potrf returned, or None - a chain with info != 0 gets NaN wherever the call writes, no other chain is touched.
+    A chain's bits are those of the host-driven loop, i descending: trsm(D[:, i], E[:, i], trans=False, info=.); potri(D[:, i],
+    symmetric=True); gemm with alpha=-1, beta=0 of the mirrored Sigma_(i+1,i+1) and that E[:, i]; gemm with alpha=-1, beta=1 into D[:, i], of
+    which the lower triangle counts - and depend on (n, T, its data) alone.  Returns (D, E).  Asynchronous on the current stream."""
+    batch, T, n, ldd, step_d, stride_d, lde, step_e, stride_e = _chain(D, E)
+    lapack.engine._potri_blocktri_batched(D, E, n, T, ldd, step_d, stride_d, lde, step_e, stride_e, batch, _info(info, D), _PACK_BI,
+                                          fill=bool(symmetric))
+    return D, E
 
 
 def _gemm_pack(transa, transb, alpha, beta):

@@ -161,3 +161,59 @@ BT_HD BtAt bt_img_tile(const int n, const int NP, const int lane, const int si, 
   a.off = bt_img_base(NP, wi) + bt_img_at(NP, row, col);
   return a;
 }
+
+// ------------------------------------------------------------------------------------------------ the selected inverse (blocktri_potri_batched.hip)
+// THE DESCENDING WALK: step 0 is position T - 1, the last step position 0, which has no predecessor.  What position pos - 1 needs is asked
+// of bt_tri_at and bt_ecol_at at pos - 1: both are off at position -1.
+BT_HD constexpr int64_t bt_walk_pos(const int64_t T, const int64_t step) { return T - 1 - step; }
+BT_HD constexpr bool bt_has_prev(const int64_t pos) { return pos > 0; }
+
+// the store of diagonal block `pos` from the mirrored area: lane -> row, column c; fill = 0: the upper triangle (bt_tri_at's set), else the FULL block
+BT_HD BtAt bt_full_at(const BtGeo& g, const int64_t wg, const int lane, const int64_t pos, const int c, const int fill) {
+  const int r = bt_idx(g.NP, lane);
+  BtAt a;
+  a.on = bt_live(g, wg, lane) && pos >= 0 && pos < g.T && r < g.n && c >= 0 && c < g.n && (fill != 0 || r <= c);
+  a.off = bt_block(g, bt_chain(g.NP, wg, lane), pos) + r + (int64_t)c * g.ld;
+  return a;
+}
+
+// TILE of coupling block `pos` (the store of C_pos from the accumulators): register r of tile (si, sj)
+BT_HD BtAt bt_etile_at(const BtGeo& g, const int64_t wg, const int lane, const int64_t pos, const int si, const int sj, const int r) {
+  const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
+  const int row = bt_idx(g.NP, wi), col = bt_idx(g.NP, wj);
+  BtAt a;
+  a.on = bt_group(g.NP, wi) == bt_group(g.NP, wj) && row < g.n && col < g.n && bt_live(g, wg, wi) && pos >= 0 && bt_has_next(g.T, pos);
+  a.off = bt_block(g, bt_chain(g.NP, wg, wi), pos) + row + (int64_t)col * g.ld;
+  return a;
+}
+
+// An exchange area read by bt_x_slab holds element (x, k) of the block of wave index w = group NP + x at line k, word w.  Three stores fill one:
+// the lane that owns COLUMN k = lane % NP of its group's block (G_i after the substitution) writes its rows x along its own line;
+BT_HD constexpr int bt_xt_own(const int NP, const int x, const int lane) { return bt_idx(NP, lane) * BT_LDX + bt_group(NP, lane) * NP + x; }
+// register r of tile (si, sj) holds element (row, col) of the block of wave row wi (C_i for the second product): line col, word wi;
+BT_HD BtAt bt_xt_tile(const int n, const int NP, const int lane, const int si, const int sj, const int r) {
+  const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
+  BtAt a;
+  a.on = bt_group(NP, wi) == bt_group(NP, wj) && bt_idx(NP, wi) < n && bt_idx(NP, wj) < n;
+  a.off = bt_idx(NP, wj) * BT_LDX + wi;
+  return a;
+}
+// THE MIRRORED AREA: register r of an upper tile holds element (row, col), row <= col, of the symmetric block: it goes to line row, word wj
+// and (mirror, row < col only) to line col, word wi - every word (x, k), x, k < n, of every group exactly once.  Lane l then finds column
+// cc of row l % NP of its group's block at bt_x_own(cc, l).
+BT_HD BtAt bt_sig_tile(const int n, const int NP, const int lane, const int si, const int sj, const int r, const bool mirror) {
+  const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
+  const int row = bt_idx(NP, wi), col = bt_idx(NP, wj);
+  BtAt a;
+  a.on = bt_group(NP, wi) == bt_group(NP, wj) && col < n && (mirror ? row < col : row <= col);
+  a.off = mirror ? col * BT_LDX + wi : row * BT_LDX + wj;
+  return a;
+}
+// both exchange areas (contiguous) start as +0.0: pass j of the lanes over 2 bt_x_size(NP) doubles
+BT_HD constexpr int bt_x_clear_passes(const int NP) { return (2 * bt_x_size(NP) + 63) / 64; }
+BT_HD BtAt bt_x_clear(const int NP, const int lane, const int j) {
+  BtAt a;
+  a.off = (int64_t)j * 64 + lane;
+  a.on = a.off < 2 * bt_x_size(NP);
+  return a;
+}

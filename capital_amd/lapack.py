@@ -71,6 +71,7 @@ class Method(enum.IntEnum):
     AlapackPstrfVbatched = 0x1F        # extension: not in the reference's enum
     AlapackPotrfBlocktriBatched = 0x20 # extension: not in the reference's enum
     AlapackPotrsBlocktriBatched = 0x21 # extension: not in the reference's enum
+    AlapackPotriBlocktriBatched = 0x22 # extension: not in the reference's enum
 
 
 class ArgPack_potrf:
@@ -257,6 +258,12 @@ class ArgPack_potrs_blocktri_batched:
     def __init__(self, order, uplo, half=0):
         self.method = Method.AlapackPotrsBlocktriBatched
         self.order, self.uplo, self.half = Order(order), UpLo(uplo), int(half)      # half: 0 both sweeps, 1 forward only, 2 backward only
+
+
+class ArgPack_potri_blocktri_batched:
+    def __init__(self, order, uplo):
+        self.method = Method.AlapackPotriBlocktriBatched
+        self.order, self.uplo = Order(order), UpLo(uplo)
 
 
 BATCHED_SMALL_MAX = 64      # cap_dpotrf_batched / cap_dpotrs_batched: a wavefront per block
@@ -453,6 +460,21 @@ class engine:
                                            lde, step_e, stride_e, dptr(matrixB), ldb, stride_b, engine._batched_info(info, batch), batch,
                                            cur_stream(stream))
         _lib.check(st, "lapack::engine::_potrs_blocktri_batched")
+
+    @staticmethod
+    def _potri_blocktri_batched(matrixD, matrixE, n, T, ldd, step_d, stride_d, lde, step_e, stride_e, batch, info, srcPackage, fill=False, stream=None):
+        """The factors _potrf_blocktri_batched left in matrixD and matrixE (same addressing, n <= 64) <- the block-tridiagonal part of the
+        inverses of the chains, in place, in one launch (cap_dpotri_blocktri_batched): the upper triangle of D_i <- that of Sigma_(i,i), E_i <-
+        Sigma_(i,i+1); fill: the strictly lower triangles of the D blocks become the mirror.  info: what _potrf_blocktri_batched returned,
+        or None; a chain with info != 0 gets NaN wherever the call writes.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        if n > BATCHED_SMALL_MAX:
+            raise _lib.CapitalError("block-tridiagonal inverse: blocks of n = %d rows exceed the limit of %d rows per block" % (n, BATCHED_SMALL_MAX))
+        L = _lib.lib()
+        st = L.cap_dpotri_blocktri_batched(int(srcPackage.uplo), 1 if fill else 0, n, T, dptr(matrixD), ldd, step_d, stride_d, dptr(matrixE), lde,
+                                           step_e, stride_e, engine._batched_info(info, batch), batch, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potri_blocktri_batched")
 
     @staticmethod
     def _batched_info(info, batch):

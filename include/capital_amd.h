@@ -587,6 +587,35 @@ int cap_dpotrs_blocktri_batched(int uplo, int half, int64_t n, int64_t T, int64_
                                 int64_t stride_d, const double* E, int64_t lde, int64_t step_e, int64_t stride_e, double* B, int64_t ldb,
                                 int64_t stride_b, const int* info, int64_t batch, void* stream);
 
+/* Batched BLOCK-TRIDIAGONAL SELECTED INVERSE (csrc/blocktri_potri_batched.hip): the marginal covariances of the chains above from their
+ * factors - the diagonal blocks Sigma_(i,i) and the lag-one blocks Sigma_(i,i+1) of Sigma = A_c^-1, the other half of every smoother and
+ * Gauss-Markov field fit - without forming the (T n) x (T n) inverse.  D, E and their layout are what cap_dpotrf_blocktri_batched left:
+ * U_i in the upper triangle of D_i, W_i = R[i, i + 1] in E_i.  With G_i = U_i^-1 W_i, positions DESCENDING, in place:
+ *   P_i = U_i^-1 U_i^-T;   Sigma_(T-1,T-1) = P_(T-1);   C_i = Sigma_(i,i+1) = -G_i Sigma_(i+1,i+1);   Sigma_(i,i) = P_i - C_i G_i^T.
+ * The upper triangle of D_i becomes that of Sigma_(i,i), E_i becomes C_i.  Read ROW-major the same memory holds Sigma[block i, block i] in
+ * the lower triangle of D[c][i] and Sigma[block i + 1, block i] in E[c][i]: the block-tridiagonal part of the inverse.  fill = 1: the
+ * strictly lower triangle of every D block becomes the bit-identical mirror, copied and never computed a second time; fill = 0: it is
+ * never addressed.  info is read and may be NULL: a chain with info[c] != 0 gets NaN wherever the call writes and no other chain is
+ * touched.  A zero on a diagonal is not detected (as cap_dtrtri_batched).  The factor is overwritten: clone it first if it is still needed.
+ * THE BIT CONTRACT IS A COMPOSITION: a chain's D and E are, bit for bit, what the host-driven loop gives on the chain's blocks, positions
+ * descending: 1. cap_dtrsm_batched(CAP_NOTRANS) with U_i and the chain's info on the n columns of E_i -> G_i; 2. cap_dpotri_batched(fill = 1)
+ * on U_i -> P_i; 3. cap_dgemm_batched(CAP_NOTRANS, CAP_NOTRANS, alpha = -1, beta = 0) of G_i and the MIRRORED Sigma_(i+1,i+1) -> C_i (every
+ * element its own chain on the fp64 16 x 16 x 4 MFMA from a zero accumulator, K ascending, rows at or beyond n as +0.0, t = alpha s);
+ * 4. cap_dgemm_batched(CAP_NOTRANS, CAP_TRANS, alpha = -1, beta = 1) of C_i and G_i into P_i, out = fma(beta, p, t), uncontracted - ONLY THE
+ * UPPER TRIANGLE of that result is Sigma_(i,i) (the two triangles of the product differ in rounding) and the operand of position i - 1 is
+ * the mirror of that triangle.  CONSEQUENCES: a chain's bits depend on (n, T, its data) alone - not on batch, the chain's index, any
+ * leading dimension, step or stride, the chains that share its wavefront or fill.
+ * ONE launch per call on a 1-D grid - a wavefront carries 64 / NP chains and walks positions T - 1 .. 0 inside the kernel - no `work`
+ * argument, no scratch, no allocation, no memset, no atomics, no helper stream, nothing between workgroups; asynchronous on `stream`;
+ * 64-bit offsets.  Position 0 has no predecessor, position T - 1 no coupling block, T = 1 addresses no E at all (E may then be NULL).  Pad
+ * rows, the gaps between blocks and chains and everything behind the last block are never addressed.
+ * Argument rules, in this order, all decided before any device call: 1. n, T or batch < 0 -> CAP_ERR_ARG; 2. with n T batch > 0 a NULL D,
+ * a NULL E with T > 1 -> CAP_ERR_ARG; 3. the layout rule of the factor (rule 3 above, without B), in 128-bit arithmetic -> CAP_ERR_ARG;
+ * 4. fill outside 0 .. 1 -> CAP_ERR_ARG; 5. uplo = CAP_LOWER -> CAP_ERR_UNSUPPORTED; 6. n > 64 -> CAP_ERR_UNSUPPORTED; 7. T n > 2^31 - 1 ->
+ * CAP_ERR_UNSUPPORTED; 8. a grid beyond one dimension -> CAP_ERR_UNSUPPORTED; 9. nothing to do (n, T or batch = 0) -> CAP_OK, nothing touched. */
+int cap_dpotri_blocktri_batched(int uplo, int fill, int64_t n, int64_t T, double* D, int64_t ldd, int64_t step_d, int64_t stride_d, double* E,
+                                int64_t lde, int64_t step_e, int64_t stride_e, const int* info, int64_t batch, void* stream);
+
 /* Batched PIVOTED Cholesky factorization for symmetric positive SEMIdefinite blocks of up to 64 rows (csrc/pstrf_batched.hip): cap_dpstrf
  * on every block of a batch in ONE launch - numerical rank, a factor that survives zero pivots, the trace error of the low-rank
  * approximation - where cap_dpotrf_batched turns a block into NaN at the first pivot that is not > 0.  For every block
