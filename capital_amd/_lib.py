@@ -58,6 +58,13 @@ SIGNATURES = {
     "cap_dpotrf_blocktri_batched": (cint, [cint, i64, i64, ptr, i64, i64, i64, ptr, i64, i64, i64, ptr, ptr, i64, ptr]),
     "cap_dpotrs_blocktri_batched": (cint, [cint, cint, i64, i64, i64, ptr, i64, i64, i64, ptr, i64, i64, i64, ptr, i64, i64, ptr, i64, ptr]),
     "cap_dpotri_blocktri_batched": (cint, [cint, cint, i64, i64, ptr, i64, i64, i64, ptr, i64, i64, i64, ptr, i64, ptr]),
+    "cap_blocktri_plan_create": (cint, [i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(ptr)]),
+    "cap_blocktri_plan_destroy": (cint, [ptr]),
+    "cap_blocktri_plan_info": (i64, [ptr, cint]),
+    "cap_blocktri_plan_order": (cint, [ptr, C.POINTER(i64), i64]),
+    "cap_dpotrf_blocktri_vbatched": (cint, [ptr, cint, i64, ptr, i64, i64, ptr, i64, i64, ptr, ptr, ptr]),
+    "cap_dpotrs_blocktri_vbatched": (cint, [ptr, cint, cint, i64, i64, ptr, i64, i64, ptr, i64, i64, ptr, i64, ptr, ptr]),
+    "cap_dpotri_blocktri_vbatched": (cint, [ptr, cint, cint, i64, ptr, i64, i64, ptr, i64, i64, ptr, ptr]),
     "cap_dsymm_batched": (cint, [cint, cint, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, dbl, ptr, i64, i64, ptr, i64, i64, i64, ptr]),
     "cap_dsymm_vbatched": (cint, [ptr, cint, cint, i64, dbl, ptr, ptr, i64, dbl, ptr, i64, ptr, i64, ptr]),
     "cap_dlansy_batched": (cint, [cint, cint, i64, ptr, i64, i64, i64, ptr, ptr]),

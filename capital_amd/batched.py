@@ -29,6 +29,8 @@ random fields, splines), T diagonal blocks of n <= 64 rows each, factored and so
 inside the kernel (cap_dpotrf_blocktri_batched / cap_dpotrs_blocktri_batched, csrc/blocktri_batched.hip).
 blocktri_potri: the MARGINAL COVARIANCES of those chains from the factor - the diagonal blocks and the lag-one blocks of the inverse, the
 smoother's other half - in one launch, without the (T n) x (T n) inverse (cap_dpotri_blocktri_batched, csrc/blocktri_potri_batched.hip).
+VarChains: those three for chains of DIFFERENT lengths - a plan built once from host-side lengths (cap_blocktri_plan,
+csrc/blocktri_vbatched.hip), one launch per call, every chain bit for bit what the fixed-length function gives for it alone.
 There is no CPU path and no fallback: anything else raises CapitalError."""
 import ctypes
 
@@ -1043,3 +1045,166 @@ class VarBatch:
             if self.sizes[i]:
                 self.block(A, i).copy_(b)
         return A[:self.total]
+
+
+class VarChains:
+    """A batch of block-tridiagonal SPD chains of DIFFERENT lengths T_c >= 0 (ragged time series, smoothers, state-space likelihoods) in
+    ONE pair of tensors: D is a sequence of n x n SLOTS, chain c owning slots first[c] .. first[c] + T_c - 1, and E is addressed with the
+    SAME slot indices - E[first[c] + i] couples positions i and i + 1 of chain c, the last slot of every chain is never touched - so D and
+    E can be two tensors of one shape.  lengths, first: host sequences of ints; first=None: the chains lie back to back in batch order.
+    The plan (cap_blocktri_plan) knows no n: it serves any n <= 64, one n per call.  It sorts the chains once by length (descending,
+    stable: .order) so that the chains of a wavefront have neighbouring lengths, and lives on the device that is current when it is made;
+    building and freeing it may synchronise, no other method does.  It is reusable for any number of calls, from several streams at once.
+    Every call is ONE launch, and every chain gets, BIT FOR BIT, what blocktri_potrf / blocktri_potrs / blocktri_potri give for it alone
+    (a batch of one chain of T_c positions) - whichever chains travel with it, whatever first, the batch order and the strides.
+    Never touched: slots no chain owns, every chain's last slot of E, pad rows and gaps, what torch reads as the strictly upper triangles of
+    the D blocks (unless symmetric=True), and everything of a chain with T_c = 0 (its info and logdet are 0).
+    .lengths / .first / .row_offsets: tuples in batch order (row_offsets: the prefix sum of the lengths - the block rows of the stacked
+    right-hand sides); .slots: slots D must hold; .eslots: slots E must hold (0: E may be None); .rows: sum of the lengths; .tmax: the
+    longest chain; .order: the plan's list; .batch.  Negative lengths or slots and overlapping chains raise CapitalError."""
+
+    def __init__(self, lengths, first=None):
+        self.lengths = tuple(int(x) for x in lengths)
+        batch = len(self.lengths)
+        if first is not None and len(first) != batch:
+            raise _lib.CapitalError("first must have one entry per chain (%d), got %d" % (batch, len(first)))
+        arr = lambda seq: (ctypes.c_int64 * max(batch, 1))(*[int(x) for x in seq]) if seq is not None else None
+        L = _lib.lib()
+        self._L, self._plan = L, ctypes.c_void_p()
+        _lib.check(L.cap_blocktri_plan_create(batch, arr(self.lengths), arr(first), ctypes.byref(self._plan)), "VarChains")
+        self.batch = batch
+        rows, at = [], 0
+        for t in self.lengths:
+            rows.append(at)
+            at += t
+        self.row_offsets = tuple(rows)
+        self.first = tuple(int(x) for x in first) if first is not None else self.row_offsets
+        self.slots = int(L.cap_blocktri_plan_info(self._plan, 1))
+        self.eslots = int(L.cap_blocktri_plan_info(self._plan, 2))
+        self.rows = int(L.cap_blocktri_plan_info(self._plan, 3))
+        self.tmax = int(L.cap_blocktri_plan_info(self._plan, 4))
+        order = (ctypes.c_int64 * max(batch, 1))()
+        _lib.check(L.cap_blocktri_plan_order(self._plan, order, batch), "VarChains")
+        self.order = tuple(int(order[k]) for k in range(batch))
+        self.device = torch.cuda.current_device() if torch.cuda.is_available() else None
+
+    def __del__(self):
+        plan, self._plan = getattr(self, "_plan", None), None
+        if plan:
+            self._L.cap_blocktri_plan_destroy(plan)
+
+    def _slots_of(self, t, name, need, n=None):
+        """(n, ld, step) of a (slots, n, n) tensor whose t[s] is read as column-major memory with ld = stride(1)"""
+        _check(t, name, (3,))
+        k, r, c = t.shape
+        if r != c or k < need or (n is not None and r != n):
+            raise _lib.CapitalError("%s must be (at least %d, n, n)%s, got shape %s" % (name, need, "" if n is None else " with n = %d" % n, tuple(t.shape)))
+        if r > 64:
+            raise _lib.CapitalError("block-tridiagonal Cholesky takes blocks of at most 64 rows, got n = %d" % r)
+        if t.device.index != self.device:
+            raise _lib.CapitalError("%s lives on device %s, the plan on device %s" % (name, t.device.index, self.device))
+        if t.numel() == 0:
+            return r, max(r, 1), max(r * r, 1)
+        if r > 1 and t.stride(2) != 1:
+            raise _lib.CapitalError("%s must have stride(-1) == 1, got strides %s" % (name, t.stride()))
+        ld = t.stride(1) if r > 1 else max(t.stride(1), 1)
+        step = t.stride(0)
+        if ld < r or (k > 1 and step < ld * r):
+            raise _lib.CapitalError("%s: blocks overlap (strides %s)" % (name, t.stride()))
+        return r, ld, max(step, 0)
+
+    def _pair(self, D, E):
+        n, ldd, step_d = self._slots_of(D, "D", self.slots)
+        if E is None:
+            if self.eslots > 0:
+                raise _lib.CapitalError("E may be None only when no chain has more than one position")
+            return n, ldd, step_d, max(n, 1), max(n * n, 1)
+        _, lde, step_e = self._slots_of(E, "E", self.eslots, n)
+        (a0, a1), (b0, b1) = _span(D), _span(E)
+        if a0 < b1 and b0 < a1:
+            raise _lib.CapitalError("D and E overlap")
+        return n, ldd, step_d, lde, step_e
+
+    def potrf(self, D, E, logdet=False):
+        """Cholesky factors of all chains, in place, in ONE launch.  D: fp64 device tensor (>= .slots, n, n), n <= 64; E: (>= .eslots, n, n)
+        with E[first_c + i] = A_c[block i + 1, block i] in torch's reading, or None when .eslots == 0.  Both follow blocktri_potrf's
+        reading and layout freedoms (stride(-1) == 1, stride(-2) >= n, stride(0) >= stride(-2) n): L_ii replaces the LOWER triangle of
+        D[first_c + i], L_(i+1, i) replaces E[first_c + i].  Returns info (int32, batch order: 0, or the 1-based row inside chain c's own
+        T_c n system of the first pivot that is not > 0 - from there on the chain holds NaN; 0 for an empty chain), or (info, logdet).
+        Chain c's bits are those of blocktri_potrf on it alone.  Asynchronous on the current stream; nothing is read back."""
+        n, ldd, step_d, lde, step_e = self._pair(D, E)
+        info, ld = lapack.engine._potrf_blocktri_vbatched(self._plan, D, E, n, ldd, step_d, lde, step_e, self.batch, _PACK_BF,
+                                                          want_logdet=bool(logdet))
+        return (info, ld) if logdet else info
+
+    def potrs(self, D, E, B, info=None, half=None):
+        """Solves A_c x = b_c for all chains in place with the factors potrf left in D and E, in ONE launch.  B: fp64 device tensor of
+        shape (rows n,) or (nrhs, rows n) with stride(-1) == 1 - every right-hand side is the stacked vector, chain c owning entries
+        n row_offsets[c] .. n (row_offsets[c] + T_c).  half: None / "forward" / "backward" as in blocktri_potrs; "forward" followed by
+        "backward" leaves the bits of the full solve.  info: what potrf returned, or None - a chain with info != 0 gets NaN.
+        Chain c's bits are those of blocktri_potrs on it alone.  Returns B.  Asynchronous on the current stream."""
+        if half not in _PACK_BS:
+            raise _lib.CapitalError("half must be None, 'forward' or 'backward', got %r" % (half,))
+        n, ldd, step_d, lde, step_e = self._pair(D, E)
+        _check(B, "B", (1, 2))
+        B2 = B.unsqueeze(0) if B.dim() == 1 else B
+        total = self.rows * n
+        if B2.shape[1] != total:
+            raise _lib.CapitalError("B must be (rows n,) or (nrhs, rows n) with rows n = %d, got shape %s" % (total, tuple(B.shape)))
+        nrhs = B2.shape[0]
+        if total > 1 and B2.stride(1) != 1:
+            raise _lib.CapitalError("every right-hand side of B must be contiguous, got strides %s" % (B.stride(),))
+        ldb = B2.stride(0) if nrhs > 1 else max(total, 1)
+        if ldb < total:
+            raise _lib.CapitalError("B: right-hand sides overlap (strides %s)" % (B.stride(),))
+        if B.device != D.device:
+            raise _lib.CapitalError("D and B live on different devices")
+        for t, name in ((D, "D"), (E, "E")):
+            if t is not None:
+                (a0, a1), (b0, b1) = _span(t), _span(B)
+                if a0 < b1 and b0 < a1:
+                    raise _lib.CapitalError("%s and B overlap" % name)
+        lapack.engine._potrs_blocktri_vbatched(self._plan, D, E, B2, n, nrhs, ldd, step_d, lde, step_e, ldb, self.batch, _info(info, D), _PACK_BS[half])
+        return B
+
+    def potri(self, D, E, info=None, symmetric=False):
+        """The marginal covariances of all chains from the factors potrf left in D and E, in place, in ONE launch: afterwards the LOWER
+        triangle of D[first_c + i] holds Sigma_c[block i, block i] and E[first_c + i] holds Sigma_c[block i + 1, block i] in torch's
+        reading; symmetric=True makes the other triangle of every owned D block the bit-identical mirror.  info: what potrf returned, or
+        None - a chain with info != 0 gets NaN wherever the call writes.  Chain c's bits are those of blocktri_potri on it alone.
+        Returns (D, E).  Asynchronous on the current stream."""
+        n, ldd, step_d, lde, step_e = self._pair(D, E)
+        lapack.engine._potri_blocktri_vbatched(self._plan, D, E, n, ldd, step_d, lde, step_e, self.batch, _info(info, D), _PACK_BI,
+                                               fill=bool(symmetric))
+        return D, E
+
+    def chain(self, X, c):
+        """The view X[first_c : first_c + T_c] of chain c's slots of D (for E: its last entry is the slot that is never touched)"""
+        return X[self.first[c]:self.first[c] + self.lengths[c]]
+
+    def pack(self, chains, device=None):
+        """(D, E): two zero-filled fp64 device tensors of shape (max(slots, 1), n, n) that hold chains[c] = (D_c, E_c) - D_c (T_c, n, n) and
+        E_c (T_c - 1, n, n) or None, any dtype / device - in chain c's slots: chain(D, c) gives D_c back, chain(E, c)[:-1] gives E_c."""
+        if len(chains) != self.batch:
+            raise _lib.CapitalError("pack needs one (D, E) pair per chain (%d), got %d" % (self.batch, len(chains)))
+        if device is None and self.device is None:
+            raise _lib.CapitalError("there is no device to pack to - there is no CPU path")
+        n = None
+        for c, (Dc, Ec) in enumerate(chains):
+            T = self.lengths[c]
+            if not isinstance(Dc, torch.Tensor) or Dc.dim() != 3 or Dc.shape[0] != T or Dc.shape[1] != Dc.shape[2] or (n is not None and Dc.shape[1] != n):
+                raise _lib.CapitalError("chain %d: D must be a (%d, n, n) tensor, got %s" % (c, T, tuple(getattr(Dc, "shape", ()))))
+            n = Dc.shape[1]
+            if T > 1 and (not isinstance(Ec, torch.Tensor) or tuple(Ec.shape) != (T - 1, n, n)):
+                raise _lib.CapitalError("chain %d: E must be a (%d, %d, %d) tensor, got %s" % (c, T - 1, n, n, tuple(getattr(Ec, "shape", ()))))
+        n = n or 0
+        dev = torch.device("cuda", self.device if device is None else device)
+        D = torch.zeros((max(self.slots, 1), n, n), dtype=torch.float64, device=dev)
+        E = torch.zeros((max(self.slots, 1), n, n), dtype=torch.float64, device=dev)
+        for c, (Dc, Ec) in enumerate(chains):
+            T = self.lengths[c]
+            if T:
+                self.chain(D, c).copy_(Dc)
+            if T > 1:
+                self.chain(E, c)[:-1].copy_(Ec)
+        return D, E

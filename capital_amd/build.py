@@ -29,7 +29,8 @@ NO_SCRATCH = ("dgemm_tn_dma_kernel", "gram256_kernel", "qrapply256_kernel", "bf1
               "tri_vbatched_blocked_kernel", "syrk_batched_kernel", "syrk_vbatched_kernel", "syrk_batched_blocked_kernel",
               "syrk_vbatched_blocked_kernel", "symm_batched_kernel", "symm_vbatched_kernel", "symm_batched_blocked_kernel",
               "symm_vbatched_blocked_kernel", "symm_copy_upper_kernel", "symm_rcond_kernel", "pstrf_batched_kernel", "pstrf_vbatched_kernel",
-              "gemm_batched_kernel", "gemm_batched_blocked_kernel", "blocktri_potrf_kernel", "blocktri_potrs_kernel", "blocktri_potri_kernel")
+              "gemm_batched_kernel", "gemm_batched_blocked_kernel", "blocktri_potrf_kernel", "blocktri_potrs_kernel", "blocktri_potri_kernel",
+              "blocktri_vpotrf_kernel", "blocktri_vpotrs_kernel", "blocktri_vpotri_kernel")
 
 
 def sources():

@@ -217,3 +217,108 @@ BT_HD BtAt bt_x_clear(const int NP, const int lane, const int j) {
   a.on = a.off < 2 * bt_x_size(NP);
   return a;
 }
+
+// ------------------------------------------------------------------------------------------------ ragged chains (blocktri_vbatched.hip)
+// CHAINS OF DIFFERENT LENGTHS on a plan: D and E are ONE sequence of n x n slots, `step` apart (BtGeo::stride, T and batch are not used);
+// chain c owns slots first .. first + T - 1 of D, and slot first + i of E holds the coupling between its positions i and i + 1 - the last
+// slot of a chain is never addressed.  The right-hand sides are stacked: the chain owns block rows row .. row + T - 1 of B.  A wavefront
+// carries the G chains at wg G .. wg G + G - 1 of the plan's sorted list; a lane group beyond the list, or one whose chain has T = 0, is
+// DEAD: T = 0 turns every predicate off.
+// The accessors take the ADDRESSED chain as values: the lane's own chain where the lane walks a row or a column of its group, the chain of
+// the WAVE ROW (btv_row_group) where it holds a tile element or supplies a slab - a lane then asks about another group's chain.
+// POSITIONS: the wavefront walks steps 0 .. (its largest T) - 1.  Ascending (factor, forward sweep) step s is position s of every chain.
+// Descending (backward sweep, selected inverse) step s is position T - 1 - s of the ADDRESSED chain (bt_walk_pos with that chain's T):
+// every chain starts at step 0 with its own last position, exactly as the fixed-size kernels start, and a chain is active while s < T in
+// both directions - there is no joining in the middle of a walk.  What a chain does not have (position -1, position T, the coupling block
+// at T - 1) is asked of the same functions and answered `off`.
+struct BtChain {
+  int64_t first, T, row;               // first slot, positions, first block row of the stacked right-hand sides
+  int64_t id;                          // index in batch order: the entry of info and logdet
+};
+
+BT_HD constexpr int btv_row_group(const int NP, const int lane, const int s) { return bt_group(NP, s * 16 + (lane & 15)); }   // the group of the lane's wave row in slab s
+BT_HD constexpr int64_t btv_pos(const BtChain& ch, const int64_t step, const bool desc) { return desc ? bt_walk_pos(ch.T, step) : step; }
+BT_HD constexpr bool btv_active(const BtChain& ch, const int64_t pos) { return pos >= 0 && pos < ch.T; }
+BT_HD constexpr bool btv_has_next(const BtChain& ch, const int64_t pos) { return pos >= 0 && bt_has_next(ch.T, pos); }
+BT_HD constexpr bool btv_has_prev(const BtChain& ch, const int64_t pos) { return bt_has_prev(pos) && pos < ch.T; }
+BT_HD constexpr int64_t btv_block(const BtGeo& g, const BtChain& ch, const int64_t pos) { return (ch.first + pos) * g.step; }
+// the coupling block and the target segment of the solve's product at a step: ascending E_pos into segment pos + 1, descending E_(pos-1) into pos - 1
+BT_HD constexpr int64_t btv_couple_epos(const BtChain& ch, const int64_t step, const bool desc) { return desc ? btv_pos(ch, step, true) - 1 : step; }
+BT_HD constexpr int64_t btv_couple_tpos(const BtChain& ch, const int64_t step, const bool desc) { return desc ? btv_pos(ch, step, true) - 1 : step + 1; }
+
+// bt_tri_at on the lane's own chain
+BT_HD BtAt btv_tri_at(const BtGeo& g, const BtChain& ch, const int lane, const int64_t pos, const int c) {
+  const int r = bt_idx(g.NP, lane);
+  BtAt a;
+  a.on = btv_active(ch, pos) && r <= c && c < g.n;
+  a.off = btv_block(g, ch, pos) + r + (int64_t)c * g.ld;
+  return a;
+}
+// bt_next_at; ch is the chain of wave row si 16 + lane % 16
+BT_HD BtAt btv_next_at(const BtGeo& g, const BtChain& ch, const int lane, const int64_t pos, const int si, const int sj, const int r) {
+  const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
+  const int row = bt_idx(g.NP, wi), col = bt_idx(g.NP, wj);
+  BtAt a;
+  a.on = bt_group(g.NP, wi) == bt_group(g.NP, wj) && row <= col && col < g.n && btv_has_next(ch, pos);
+  a.off = btv_block(g, ch, pos + 1) + row + (int64_t)col * g.ld;
+  return a;
+}
+// bt_ecol_at on the lane's own chain
+BT_HD BtAt btv_ecol_at(const BtGeo& g, const BtChain& ch, const int lane, const int64_t pos, const int q) {
+  const int c = bt_idx(g.NP, lane);
+  BtAt a;
+  a.on = btv_has_next(ch, pos) && c < g.n && q >= 0 && q < g.n;
+  a.off = btv_block(g, ch, pos) + q + (int64_t)c * g.ld;
+  return a;
+}
+// bt_eslab_at; ch is the chain of wave row s 16 + lane % 16
+BT_HD BtAt btv_eslab_at(const BtGeo& g, const BtChain& ch, const int lane, const int64_t pos, const int s, const int q, const bool trans) {
+  const int w = s * 16 + (lane & 15), row = bt_idx(g.NP, w), k = q + (lane >> 4);
+  BtAt a;
+  a.on = btv_has_next(ch, pos) && row < g.n && k < g.n;
+  a.off = btv_block(g, ch, pos) + (trans ? k + (int64_t)row * g.ld : row + (int64_t)k * g.ld);
+  return a;
+}
+// bt_rhs_at on the lane's own chain: row (ch.row + pos) n + r of the stacked system
+BT_HD BtAt btv_rhs_at(const BtGeo& g, const BtChain& ch, const int64_t ldb, const int64_t nrhs, const int lane, const int64_t pass, const int64_t pos,
+                      const int r) {
+  const int64_t col = pass * g.NP + bt_idx(g.NP, lane);
+  BtAt a;
+  a.on = btv_active(ch, pos) && col < nrhs && r >= 0 && r < g.n;
+  a.off = col * ldb + (ch.row + pos) * g.n + r;
+  return a;
+}
+// the chain's entry of info and logdet: lane 0 of a group whose chain has a position (the entries of empty chains are not written)
+BT_HD BtAt btv_scalar_at(const int NP, const BtChain& ch, const int lane) {
+  BtAt a;
+  a.on = ch.T > 0 && bt_idx(NP, lane) == 0;
+  a.off = ch.id;
+  return a;
+}
+BT_HD BtAt btv_info_at(const BtChain& ch) {
+  BtAt a;
+  a.on = ch.T > 0;
+  a.off = ch.id;
+  return a;
+}
+// bt_full_at on the lane's own chain
+BT_HD BtAt btv_full_at(const BtGeo& g, const BtChain& ch, const int lane, const int64_t pos, const int c, const int fill) {
+  const int r = bt_idx(g.NP, lane);
+  BtAt a;
+  a.on = btv_active(ch, pos) && r < g.n && c >= 0 && c < g.n && (fill != 0 || r <= c);
+  a.off = btv_block(g, ch, pos) + r + (int64_t)c * g.ld;
+  return a;
+}
+// bt_etile_at; ch is the chain of wave row si 16 + lane % 16
+BT_HD BtAt btv_etile_at(const BtGeo& g, const BtChain& ch, const int lane, const int64_t pos, const int si, const int sj, const int r) {
+  const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
+  const int row = bt_idx(g.NP, wi), col = bt_idx(g.NP, wj);
+  BtAt a;
+  a.on = bt_group(g.NP, wi) == bt_group(g.NP, wj) && row < g.n && col < g.n && btv_has_next(ch, pos);
+  a.off = btv_block(g, ch, pos) + row + (int64_t)col * g.ld;
+  return a;
+}
+// THE TABLE of the wavefront's G <= 8 chains in LDS: BTV_TAB int64 per group (first, T, row, id); lane 0 of every group writes its entry
+constexpr int BTV_TAB = 4;
+BT_HD constexpr int btv_tab_at(const int group, const int field) { return group * BTV_TAB + field; }
+BT_HD constexpr int btv_tab_size() { return 8 * BTV_TAB; }

@@ -477,6 +477,53 @@ class engine:
         _lib.check(st, "lapack::engine::_potri_blocktri_batched")
 
     @staticmethod
+    def _potrf_blocktri_vbatched(plan, matrixD, matrixE, n, ldd, step_d, lde, step_e, batch, srcPackage, want_logdet=False, stream=None):
+        """The chains of DIFFERENT lengths that `plan` (a cap_blocktri_plan handle) describes inside the slot sequences matrixD / matrixE
+        (slot s is column-major with ld ldd at matrixD + s step_d, E likewise; n <= 64) <- their block bidiagonal Cholesky factors, in
+        place, in one launch (cap_dpotrf_blocktri_vbatched).  Every chain gets the bits _potrf_blocktri_batched gives for it alone.
+        Returns (info, logdet) in batch order as _potrf_blocktri_batched does, info[c] the row inside chain c's own system; the entries of
+        empty chains are 0 (the kernel does not write them).  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        if n > BATCHED_SMALL_MAX:
+            raise _lib.CapitalError("block-tridiagonal Cholesky: blocks of n = %d rows exceed the limit of %d rows per block" % (n, BATCHED_SMALL_MAX))
+        L = _lib.lib()
+        dev = matrixD.device if isinstance(matrixD, torch.Tensor) else torch.device("cuda", torch.cuda.current_device())
+        info = torch.zeros(max(batch, 1), dtype=torch.int32, device=dev)
+        logdet = torch.zeros(max(batch, 1), dtype=torch.float64, device=dev) if want_logdet else None
+        st = L.cap_dpotrf_blocktri_vbatched(plan, int(srcPackage.uplo), n, dptr(matrixD), ldd, step_d, dptr(matrixE), lde, step_e, info.data_ptr(),
+                                            logdet.data_ptr() if want_logdet else None, cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrf_blocktri_vbatched")
+        return info[:max(batch, 0)], (logdet[:max(batch, 0)] if want_logdet else None)
+
+    @staticmethod
+    def _potrs_blocktri_vbatched(plan, matrixD, matrixE, matrixB, n, nrhs, ldd, step_d, lde, step_e, ldb, batch, info, srcPackage, stream=None):
+        """The stacked right-hand sides matrixB ((n sum T) x nrhs, column-major, ld ldb; chain c owns the rows behind n times the prefix sum
+        of T) <- the solutions with the factors _potrf_blocktri_vbatched left, in one launch (cap_dpotrs_blocktri_vbatched); srcPackage.half
+        as in _potrs_blocktri_batched.  info: what _potrf_blocktri_vbatched returned, or None; a chain with info != 0 gets NaN.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        if n > BATCHED_SMALL_MAX:
+            raise _lib.CapitalError("block-tridiagonal Cholesky: blocks of n = %d rows exceed the limit of %d rows per block" % (n, BATCHED_SMALL_MAX))
+        L = _lib.lib()
+        st = L.cap_dpotrs_blocktri_vbatched(plan, int(srcPackage.uplo), int(srcPackage.half), n, nrhs, dptr(matrixD), ldd, step_d, dptr(matrixE), lde,
+                                            step_e, dptr(matrixB), ldb, engine._batched_info(info, batch), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potrs_blocktri_vbatched")
+
+    @staticmethod
+    def _potri_blocktri_vbatched(plan, matrixD, matrixE, n, ldd, step_d, lde, step_e, batch, info, srcPackage, fill=False, stream=None):
+        """The factors _potrf_blocktri_vbatched left <- the block-tridiagonal part of the inverses of the chains, in place, in one launch
+        (cap_dpotri_blocktri_vbatched), as _potri_blocktri_batched does for every chain alone.  Asynchronous."""
+        if srcPackage.order != Order.AlapackColumnMajor:
+            raise _lib.CapitalError("only AlapackColumnMajor is supported")
+        if n > BATCHED_SMALL_MAX:
+            raise _lib.CapitalError("block-tridiagonal inverse: blocks of n = %d rows exceed the limit of %d rows per block" % (n, BATCHED_SMALL_MAX))
+        L = _lib.lib()
+        st = L.cap_dpotri_blocktri_vbatched(plan, int(srcPackage.uplo), 1 if fill else 0, n, dptr(matrixD), ldd, step_d, dptr(matrixE), lde, step_e,
+                                            engine._batched_info(info, batch), cur_stream(stream))
+        _lib.check(st, "lapack::engine::_potri_blocktri_vbatched")
+
+    @staticmethod
     def _batched_info(info, batch):
         if info is not None and (not isinstance(info, torch.Tensor) or not info.is_cuda or info.dtype != torch.int32
                                  or info.numel() < batch or not info.is_contiguous()):

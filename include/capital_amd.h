@@ -616,6 +616,51 @@ int cap_dpotrs_blocktri_batched(int uplo, int half, int64_t n, int64_t T, int64_
 int cap_dpotri_blocktri_batched(int uplo, int fill, int64_t n, int64_t T, double* D, int64_t ldd, int64_t step_d, int64_t stride_d, double* E,
                                 int64_t lde, int64_t step_e, int64_t stride_e, const int* info, int64_t batch, void* stream);
 
+/* RAGGED block-tridiagonal chains (csrc/blocktri_vbatched.hip): the three entries above for a batch whose chains have DIFFERENT lengths
+ * T_c >= 0 - time series, smoothers and likelihoods come in ragged batches - on a plan over the lengths, as the other members of the
+ * family have a _vbatched form on a cap_vbatch_plan.  ONE launch per call; every chain gets, bit for bit, what the fixed-size entry
+ * writes for it alone (T = T_c, batch = 1): D, E, the solutions, info[c], logdet[c] - whichever chains share its wavefront or the batch,
+ * whatever `first`, the batch order, the leading dimensions and the steps, with and without fill; half = 1 followed by half = 2 leaves the
+ * bits of half = 0, and the composition contracts of the fixed-size entries carry over.
+ * THE PLAN.  cap_blocktri_plan_create(batch, T, first, &p): T and first are HOST arrays of batch entries.  D is one sequence of n x n
+ * SLOTS, step_d apart with leading dimension ldd (both given per call: the plan knows no n and serves any n <= 64, one n per call); chain
+ * c owns slots first[c] .. first[c] + T[c] - 1; first = NULL: the chains lie back to back in batch order (the prefix sum of T).  E is
+ * addressed with the SAME slot indices: slot first[c] + i holds the coupling between positions i and i + 1 of chain c, the last slot of
+ * every chain, first[c] + T[c] - 1, is never addressed (D and E can be two tensors of one shape); E may be NULL when no chain has more
+ * than one position.  T[c] = 0 is legal: nothing of that chain is touched, info[c] and logdet[c] are NOT written.
+ * create: 1. NULL out, batch < 0, NULL T with batch > 0 -> CAP_ERR_ARG; 2. a T[c] < 0 or first[c] < 0 -> CAP_ERR_ARG; 3. two non-empty
+ * chains whose slot ranges meet -> CAP_ERR_ARG; 4. sums beyond int64 -> CAP_ERR_ARG.  It sorts the chains STABLY BY T DESCENDING into one
+ * list (cap_blocktri_plan_order copies up to cap entries of it to the host): the 64 / NP chains of a wavefront are neighbours of that
+ * list, and the longest start first.  The records and the list are uploaded with synchronous copies: create and destroy MAY SYNCHRONISE,
+ * no other function does.  In a process without a device create succeeds and the plan serves _info and _order only.  The plan is read-only
+ * afterwards: usable from several streams and host threads at once, on the device that was current when it was made.
+ * cap_blocktri_plan_info(p, what): CAP_BLOCKTRI_BATCH; _SLOTS = max(first + T) over the non-empty chains; _ESLOTS = the largest addressed
+ * coupling slot + 1 (0: no chain has two positions); _ROWS = sum T; _TMAX = the longest chain; -1 for anything else or a NULL plan.
+ * THE ENTRIES.  1 <= n <= 64; the grid is ceil(batch / (64 / NP)) wavefronts over the sorted list, each walking to the largest T of its
+ * chains.  info and logdet have batch entries in BATCH order; info[c] is 0 or the 1-based row inside chain c's own T[c] n system of the
+ * first pivot that is not > 0.  B is the STACKED system, (n ROWS) x nrhs column-major with ldb >= n ROWS: chain c owns rows n row[c] ..
+ * n (row[c] + T[c]), row the prefix sum of T in batch order (as cap_dpotrs_vbatched stacks blocks).  half, fill, failure and NaN
+ * conventions are those of the fixed-size entries.  No `work`, scratch, allocation, memset, atomics or helper stream; asynchronous on
+ * `stream`; 64-bit offsets.  Pad rows, gaps between slots, slots no chain owns and every chain's last slot of E are never addressed.
+ * Argument rules, in this order, all before any device call: 1. NULL plan, n < 0 or nrhs < 0 -> CAP_ERR_ARG; 2. with something to launch
+ * a NULL D, a NULL info (factor) or B (solve), a NULL E while some chain has T > 1 -> CAP_ERR_ARG; 3. ldd < n; lde < n when E is used;
+ * step < ld n when the plan spans more than one slot; ldb < n ROWS - in 128-bit arithmetic -> CAP_ERR_ARG; 4. half or fill out of range
+ * -> CAP_ERR_ARG; 5. uplo = CAP_LOWER -> CAP_ERR_UNSUPPORTED; 6. n > 64 -> CAP_ERR_UNSUPPORTED; 7. n TMAX > 2^31 - 1 ->
+ * CAP_ERR_UNSUPPORTED; 8. a grid beyond one dimension -> CAP_ERR_UNSUPPORTED; 9. nothing to do (n = 0, an empty or all-empty plan, nrhs
+ * = 0) -> CAP_OK without a launch; 10. a plan made without a device -> CAP_ERR_HIP. */
+typedef struct cap_blocktri_plan cap_blocktri_plan;
+enum { CAP_BLOCKTRI_BATCH = 0, CAP_BLOCKTRI_SLOTS = 1, CAP_BLOCKTRI_ESLOTS = 2, CAP_BLOCKTRI_ROWS = 3, CAP_BLOCKTRI_TMAX = 4 };
+int cap_blocktri_plan_create(int64_t batch, const int64_t* T, const int64_t* first, cap_blocktri_plan** out);
+int cap_blocktri_plan_destroy(cap_blocktri_plan* p);
+int64_t cap_blocktri_plan_info(const cap_blocktri_plan* p, int what);
+int cap_blocktri_plan_order(const cap_blocktri_plan* p, int64_t* chains, int64_t cap);
+int cap_dpotrf_blocktri_vbatched(const cap_blocktri_plan* p, int uplo, int64_t n, double* D, int64_t ldd, int64_t step_d, double* E, int64_t lde,
+                                 int64_t step_e, int* info, double* logdet, void* stream);
+int cap_dpotrs_blocktri_vbatched(const cap_blocktri_plan* p, int uplo, int half, int64_t n, int64_t nrhs, const double* D, int64_t ldd,
+                                 int64_t step_d, const double* E, int64_t lde, int64_t step_e, double* B, int64_t ldb, const int* info, void* stream);
+int cap_dpotri_blocktri_vbatched(const cap_blocktri_plan* p, int uplo, int fill, int64_t n, double* D, int64_t ldd, int64_t step_d, double* E,
+                                 int64_t lde, int64_t step_e, const int* info, void* stream);
+
 /* Batched PIVOTED Cholesky factorization for symmetric positive SEMIdefinite blocks of up to 64 rows (csrc/pstrf_batched.hip): cap_dpstrf
  * on every block of a batch in ONE launch - numerical rank, a factor that survives zero pivots, the trace error of the low-rank
  * approximation - where cap_dpotrf_batched turns a block into NaN at the first pivot that is not > 0.  For every block
