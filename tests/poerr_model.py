@@ -2,7 +2,10 @@
 
 `lacn2(apply, apply_t, n)` is LAPACK's dlacn2 with its reverse communication turned into two callbacks: the start vector 1 / n, the sign
 vector (x > 0 -> 1, else -1), the stop at a repeated sign vector or an estimate that did not grow, idamax with the lowest index winning
-ties, ITMAX = 5, the final alternating-sign vector with its 2 |x|_1 / (3 n) floor.  It returns (est, number of operator applications)."""
+ties, ITMAX = 5, the final alternating-sign vector with its 2 |x|_1 / (3 n) floor.  It returns (est, number of operator applications).
+With a list as `trace` it also appends, per operator application and in order, (stage, j, est): the stage in which the result of that
+application is judged (1 the start vector, 2 / 4 a sign vector, 3 a unit vector, 5 the alternating-sign vector: the stage numbers of
+csrc/pocon.hip) and the index and the estimate as they stand after that judgement.  The results do not depend on `trace`."""
 import numpy as np
 
 EPS = 2.0 ** -53                       # dlamch('Epsilon')
@@ -18,25 +21,31 @@ def _idamax(x):
     return int(np.argmax(np.abs(x)))    # the first of equals, as idamax
 
 
-def lacn2(apply, apply_t, n):
+def lacn2(apply, apply_t, n, trace=None):
+    note = (lambda *a: None) if trace is None else (lambda stage, j, est: trace.append((stage, int(j), float(est))))
     solves = 1
     x = apply(np.full(n, 1.0 / n))
     if n == 1:
+        note(1, 0, abs(x[0]))
         return abs(x[0]), solves
     est = np.abs(x).sum()
+    note(1, 0, est)
     isgn = _sign(x)
     x = apply_t(isgn.copy()); solves += 1
     j = _idamax(x)
+    note(2, j, est)
     it = 2
     while True:
         e = np.zeros(n); e[j] = 1.0
         x = apply(e); solves += 1
         estold, est = est, np.abs(x).sum()
+        note(3, j, est)
         if np.array_equal(_sign(x), isgn) or est <= estold:
             break
         isgn = _sign(x)
         x = apply_t(isgn.copy()); solves += 1
         jlast, j = j, _idamax(x)
+        note(4, j, est)
         if x[jlast] != abs(x[j]) and it < ITMAX:
             it += 1
             continue
@@ -47,6 +56,7 @@ def lacn2(apply, apply_t, n):
     temp = 2.0 * (np.abs(x).sum() / (3 * n))
     if temp > est:
         est = temp
+    note(5, j, est)
     return est, solves
 
 

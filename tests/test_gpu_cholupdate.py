@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from tests import cholupdate_model as cm
+from tests.gpu_util import NanWork
 
 pytestmark = pytest.mark.gpu
 
@@ -70,11 +71,12 @@ def _bits(t):
 
 
 def _dcholupdate(sign, n, k, Rbuf, Vbuf, info=None):
+    """(scratch: all NaN, exactly the stated size, a sentinel behind it)"""
     L = _L()
-    work = torch.empty(max(L.cap_dcholupdate_work_size(n, k), 1), dtype=torch.float64, device=DEV)
+    work = NanWork(L.cap_dcholupdate_work_size(n, k))
     st = L.cap_dcholupdate(1, sign, n, k, Rbuf.data_ptr(), Rbuf.shape[1], Vbuf.data_ptr(), Vbuf.shape[1],
                            info.data_ptr() if info is not None else None, work.data_ptr(), _stream())
-    torch.cuda.synchronize()
+    work.check("cap_dcholupdate(n = %d, k = %d)" % (n, k))
     return st
 
 
@@ -86,7 +88,10 @@ def _upper(view):
 # every n (one and two rows, around one and two tiles of 64, several block rows, a ragged last block) and every k (one column, a padded
 # pass, a full pass, a second pass of one column, three passes) appear
 OPERATOR_CASES = [(1, 1), (1, 17), (2, 5), (2, 40), (63, 16), (63, 1), (64, 17), (64, 5), (65, 40), (65, 16), (127, 1), (127, 17),
-                  (128, 5), (128, 40), (129, 17), (129, 16), (300, 1), (300, 40), (517, 5), (517, 40)]
+                  (128, 5), (128, 40), (129, 17), (129, 16), (300, 1), (300, 40), (517, 5), (517, 40),
+                  # launch_pass<2> and <4> (k = 2 and 3 / 4) and a 1 / 8 / 16 + 16 + 1 mix on several block rows: the two instantiations the
+                  # rows above do not reach get an accuracy check of their own
+                  (65, 2), (129, 2), (64, 3), (200, 4), (129, 9), (130, 33)]
 
 
 @pytest.mark.parametrize("n,k", OPERATOR_CASES)

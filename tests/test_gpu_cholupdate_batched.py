@@ -15,6 +15,7 @@ import torch
 from tests import cholupdate_model as cm
 from tests import stream_order as SO
 from tests import vbatched_cases as VC
+from tests.gpu_util import NanWork
 
 pytestmark = pytest.mark.gpu
 
@@ -103,10 +104,10 @@ def _single(sign, R, V):
     L = _L()
     n, k = V.shape
     Rf, Vf = Flat([R], n, n * n, True), Flat([V], n, n * k, False)
-    work = torch.empty(max(L.cap_dcholupdate_work_size(n, k), 1), dtype=torch.float64, device=DEV)
+    work = NanWork(L.cap_dcholupdate_work_size(n, k))                    # all NaN, exactly the stated size, a sentinel behind it
     info = torch.full((1,), 77, dtype=torch.int32, device=DEV)
     assert L.cap_dcholupdate(1, sign, n, k, Rf.ptr(), n, Vf.ptr(), n, info.data_ptr(), work.data_ptr(), _stream()) == OK
-    torch.cuda.synchronize()
+    work.check("cap_dcholupdate(n = %d, k = %d)" % (n, k))
     return Rf.get(0), int(info.item())
 
 

@@ -9,6 +9,7 @@ import scipy.linalg as sl
 import torch
 
 from tests import poerr_model as pm
+from tests.gpu_util import NanWork
 
 pytestmark = pytest.mark.gpu
 
@@ -59,9 +60,9 @@ def _pocon(n, Rbuf, ld, anorm):
     L = _L()
     an = torch.full((1,), anorm, dtype=torch.float64, device=DEV)
     out = torch.full((3,), -5.0, dtype=torch.float64, device=DEV)
-    w = torch.empty(max(int(L.cap_dpocon_work_size(n)), 2), dtype=torch.float64, device=DEV)
+    w = NanWork(L.cap_dpocon_work_size(n))                           # all NaN, exactly the stated size, a sentinel behind it
     assert L.cap_dpocon(1, n, Rbuf.data_ptr() if Rbuf is not None else None, ld, an.data_ptr(), out.data_ptr() + 8, w.data_ptr(), _stream()) == OK
-    torch.cuda.synchronize()
+    w.check("cap_dpocon(n = %d)" % n)
     o = out.cpu().numpy()
     assert o[0] == -5.0 and o[2] == -5.0
     return o[1]
@@ -155,11 +156,10 @@ def test_plan_rcond_is_lansy_then_pocon(ci):
     ldr = C.c_int64(0)
     Rp = L.cap_cholinv_R_ptr(p.h, C.byref(ldr))
     an = torch.zeros(1, dtype=torch.float64, device=DEV); rc = torch.zeros(1, dtype=torch.float64, device=DEV)
-    w1 = torch.empty(L.cap_dlansy_work_size(n), dtype=torch.float64, device=DEV)
-    w2 = torch.empty(L.cap_dpocon_work_size(n), dtype=torch.float64, device=DEV)
+    w1, w2 = NanWork(L.cap_dlansy_work_size(n)), NanWork(L.cap_dpocon_work_size(n))
     assert L.cap_dlansy(ord('1'), 1, n, up.data_ptr(), n, an.data_ptr(), w1.data_ptr(), _stream()) == OK
     assert L.cap_dpocon(1, n, Rp, ldr.value, an.data_ptr(), rc.data_ptr(), w2.data_ptr(), _stream()) == OK
-    torch.cuda.synchronize()
+    w1.check("cap_dlansy"), w2.check("cap_dpocon")
     assert an.item() == np.abs(a).sum(0).max() or abs(an.item() - np.abs(a).sum(0).max()) <= 1e-13 * an.item()
     assert got == rc.item(), "bit for bit"
     st, got2 = p.rcond(anorm=an)

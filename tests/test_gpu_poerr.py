@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from tests import poerr_model as pm
+from tests.gpu_util import NanWork
 
 pytestmark = pytest.mark.gpu
 
@@ -141,10 +142,11 @@ def test_chunks_of_sixteen_columns_a_zero_column_and_null_outputs():
     # the same through cap_dpoerr on the plan's factor
     ldr = C.c_int64(0)
     Rp = L.cap_cholinv_R_ptr(pack._plan, C.byref(ldr))
-    w = torch.empty(L.cap_dpoerr_work_size(n, nrhs), dtype=torch.float64, device=DEV)
+    w = NanWork(L.cap_dpoerr_work_size(n, nrhs))                      # all NaN, exactly the stated size, a sentinel behind it
     f3 = torch.empty(nrhs, dtype=torch.float64, device=DEV); e3 = torch.empty(nrhs, dtype=torch.float64, device=DEV)
     assert L.cap_dpoerr(1, n, nrhs, Ad.data_ptr(), ld, Rp, ldr.value, Bd.data_ptr(), ld, Xd.data_ptr(), ld, f3.data_ptr(), e3.data_ptr(),
                         w.data_ptr(), st) == OK
+    w.check("cap_dpoerr")
     assert np.array_equal(f3.cpu().numpy(), f) and np.array_equal(e3.cpu().numpy(), e)
     for m, m0 in ((Ad, au), (Bd, b), (Xd, x)):
         assert np.array_equal(m[:, :n].cpu().numpy(), m0.T, equal_nan=True) and torch.isnan(m[:, n:]).all(), "an input was written"

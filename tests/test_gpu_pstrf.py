@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from tests import pstrf_model as pm
+from tests.gpu_util import NanWork
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +54,7 @@ def _dpstrf(A, max_rank=None, tol=-1.0):
     out_rank = torch.full((2,), -7, dtype=torch.int64, device=DEV)
     out_info = torch.full((2,), -7, dtype=torch.int32, device=DEV)
     out_resid = torch.full((2,), NAN, dtype=torch.float64, device=DEV)
-    work = torch.full((int(L.cap_dpstrf_work_size(n, mr)) + 1,), NAN, dtype=torch.float64, device=DEV)
+    work = NanWork(L.cap_dpstrf_work_size(n, mr))                    # all NaN, exactly the stated size, a sentinel of 4096 behind it
     st = L.cap_dpstrf(1, n, mr, float(tol), Abuf.data_ptr(), Abuf.shape[1], Rbuf.data_ptr(), ldr, piv.data_ptr(), out_rank.data_ptr(),
                       out_resid.data_ptr(), out_info.data_ptr(), work.data_ptr(), torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
@@ -61,7 +62,7 @@ def _dpstrf(A, max_rank=None, tol=-1.0):
     assert torch.equal(_bits(Abuf), abits), "A or its padding was written"
     assert bool(torch.isnan(Rbuf[:, mr:]).all()), "padding rows of R were written"
     assert int(piv[n]) == -7 and int(out_rank[1]) == -7 and int(out_info[1]) == -7 and bool(torch.isnan(out_resid[1]))
-    assert bool(torch.isnan(work[-1])), "the scratch was overrun"
+    work.check("cap_dpstrf(n = %d, max_rank = %d)" % (n, mr))
     R = Rbuf[:, :mr].t().cpu().numpy().copy()
     return R, piv[:n].cpu().numpy(), int(out_rank[0]), int(out_info[0]), float(out_resid[0])
 

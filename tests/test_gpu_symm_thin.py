@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests.gpu_util import NanWork
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
@@ -65,7 +67,8 @@ def _sym(rng, n):
 
 
 def _work(n, nrhs):
-    return torch.full((max(int(_L().cap_dsymm_thin_work_size(n, nrhs)), 2),), NAN, dtype=torch.float64, device=DEV)
+    """all NaN, exactly the stated size, a sentinel behind it (check())"""
+    return NanWork(_L().cap_dsymm_thin_work_size(n, nrhs))
 
 
 def _call(ab, n, nrhs, alpha, A, X, beta, B, Y, work):
@@ -93,6 +96,7 @@ def test_exact_on_padded_windows(n, nrhs):
         torch.cuda.synchronize()
         assert np.array_equal(Y.get(), _ref(ab, alpha, a, x, beta, b)), (ab, alpha, beta)
         assert Y.outside_unchanged(), "written outside Y's n rows"
+        work.check("cap_dsymm_thin")
     for w in (A, X, B):
         assert np.array_equal(w.buf.cpu().numpy(), w.host0, equal_nan=True), "an input was written"
 
@@ -122,6 +126,7 @@ def test_beta_zero_alpha_zero_and_in_place(n, nrhs):
     assert _L().cap_dsymm_thin(1, 0, n, nrhs, -1.0, A.ptr, A.ld, X.ptr, X.ld, 1.0, Yb.ptr, Yb.ld, Yb.ptr, Yb.ld, work.data_ptr(), _stream()) == OK
     torch.cuda.synchronize()
     assert np.array_equal(Yb.get(), b - a @ x) and Yb.outside_unchanged()
+    work.check("cap_dsymm_thin")
     # Y on top of A, X or work is refused
     assert _L().cap_dsymm_thin(1, 0, n, nrhs, 1.0, A.ptr, A.ld, X.ptr, X.ld, 0.0, None, 0, X.ptr, X.ld, work.data_ptr(), _stream()) == ARG
     assert _L().cap_dsymm_thin(1, 0, n, nrhs, 1.0, A.ptr, A.ld, X.ptr, X.ld, 0.0, None, 0, work.data_ptr(), n, work.data_ptr(), _stream()) == ARG
@@ -143,6 +148,7 @@ def test_two_calls_give_the_same_bits_and_the_right_product():
         torch.cuda.synchronize()
         out.append(Y.get())
     assert np.array_equal(out[0], out[1])
+    work.check("cap_dsymm_thin")
     ref = b - a @ x
     # a sum of n products in any order: |error| <= gamma_n (|A||X| + |B|) componentwise, gamma_n = n u / (1 - n u), u = 2^-53
     bound = (n * 2.0 ** -53 / (1 - n * 2.0 ** -53)) * (np.abs(a) @ np.abs(x) + np.abs(b))
@@ -152,9 +158,9 @@ def test_two_calls_give_the_same_bits_and_the_right_product():
 def _lansy(n, A):
     L = _L()
     out = torch.full((3,), -5.0, dtype=torch.float64, device=DEV)
-    work = torch.full((max(int(L.cap_dlansy_work_size(n)), 2),), NAN, dtype=torch.float64, device=DEV)
+    work = NanWork(L.cap_dlansy_work_size(n))
     assert L.cap_dlansy(ord('1'), 1, n, A.ptr if A else None, A.ld if A else 0, out.data_ptr() + 8, work.data_ptr(), _stream()) == OK
-    torch.cuda.synchronize()
+    work.check("cap_dlansy(n = %d)" % n)
     o = out.cpu().numpy()
     assert o[0] == -5.0 and o[2] == -5.0
     return o[1]
@@ -168,9 +174,10 @@ def test_lansy_exact(n):
     assert _lansy(n, A) == np.abs(a).sum(0).max()
     for norm in (b'O', b'I'):
         out = torch.zeros(1, dtype=torch.float64, device=DEV)
-        work = torch.empty(max(int(_L().cap_dlansy_work_size(n)), 2), dtype=torch.float64, device=DEV)
+        work = NanWork(_L().cap_dlansy_work_size(n))
         assert _L().cap_dlansy(ord(norm), 1, n, A.ptr, A.ld, out.data_ptr(), work.data_ptr(), _stream()) == OK
         assert out.item() == np.abs(a).sum(0).max()
+        work.check("cap_dlansy(n = %d)" % n)
 
 
 @pytest.mark.parametrize("n", (65, 2 * S + 1))
