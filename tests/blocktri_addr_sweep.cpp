@@ -1,6 +1,7 @@
-// TEST INFRASTRUCTURE of tests/test_blocktri_addr.py: the loops of capital_amd/csrc/blocktri_batched.hip (blocktri_potrf_kernel,
-// blocktri_potrs_kernel with half = 0, 1, 2, bt_couple) replayed on the CPU, workgroup by workgroup and lane by lane, with the address
-// functions the kernels themselves call (capital_amd/csrc/blocktri_addr.h).  Reads one launch per line from stdin:
+// TEST INFRASTRUCTURE of tests/test_blocktri_addr.py: the loops of capital_amd/csrc/blocktri_kernels.h (bt_factor, bt_solve with
+// half = 0, 1, 2, bt_couple) as blocktri_batched.hip launches them - the chain of a lane group from bt_chain_fixed, a walk of T steps -
+// replayed on the CPU, workgroup by workgroup and lane by lane, with the address functions the kernels themselves call
+// (capital_amd/csrc/blocktri_addr.h).  Reads one launch per line from stdin:
 //   n T batch nrhs ldd step_d stride_d lde step_e stride_e ldb stride_b eblocks
 // eblocks is the number of coupling blocks per chain the E operand really holds - T - 1 for every launch the library makes; a line that
 // says less is a planted fault (the kernel would address a coupling block the chain does not have).
@@ -99,13 +100,16 @@ int main() {
     D.init();
     E.init();
     const long long img = (long long)G * bt_img_size(NP), xs = bt_x_size(NP);
+    // the chain of a lane (its own group's) and of its wave row in slab s, as BtFixed answers
+    auto own_of = [&](long long wg, int lane) { return bt_chain_fixed(gd, ge, stride_b, wg, bt_group(NP, lane)); };
+    auto row_of = [&](long long wg, int lane, int s) { return bt_chain_fixed(gd, ge, stride_b, wg, bt_row_group(NP, lane, s)); };
 
     // ---------------------------------------------------------------------------------------------- the factor
     std::vector<int> scalars((size_t)batch, 0);
     for (long long wg = 0; wg < nwg; wg++) {
       for (int lane = 0; lane < 64; lane++)
         for (int cc = 0; cc < n; cc++) {
-          const BtAt at = bt_tri_at(gd, wg, lane, 0, cc);
+          const BtAt at = bt_tri_at(gd, own_of(wg, lane), lane, 0, cc);
           if (at.on) { D.rd[D.at(at.off, bt_chain(NP, wg, lane), 0, lane % NP, cc, true, wg, lane)]++; lds(bt_img_base(NP, lane) + bt_img_at(NP, lane % NP, cc), img, "image", wg, lane, 0); }
         }
       for (long long pos = 0; pos < T; pos++) {
@@ -113,8 +117,10 @@ int main() {
         std::vector<int> imgw((size_t)img, 0);
         for (int lane = 0; lane < 64; lane++) {
           const long long chain = bt_chain(NP, wg, lane);
+          const BtChain own = own_of(wg, lane);
+          if (own.T != (chain < batch ? T : 0) || own.id != chain) fail("chain", "not the lane group's chain", own.id, wg, lane, pos);
           for (int i = 0; i < n; i++) {            // the request for E_pos: asked at every position, the last one included
-            const BtAt at = bt_ecol_at(ge, wg, lane, pos, i);
+            const BtAt at = bt_ecol_at(ge, own, lane, pos, i);
             if (at.on && !has) fail("E", "a coupling block at position T - 1", at.off, wg, lane, pos);
             if (at.on) E.rd[E.at(at.off, chain, pos, i, lane % NP, false, wg, lane)]++;
           }
@@ -122,11 +128,12 @@ int main() {
             for (int sj = 0; sj < 4; sj++)
               for (int r = 0; r < 4; r++) {
                 if (!bt_tile(NP, si, sj, true) || !bt_slab_on(NP, si, n) || !bt_slab_on(NP, sj, n)) continue;
-                const BtAt at = bt_next_at(gd, wg, lane, pos, si, sj, r);
+                const BtAt at = bt_next_at(gd, row_of(wg, lane, si), lane, pos, si, sj, r);
                 if (at.on && !has) fail("D", "a successor at position T - 1", at.off, wg, lane, pos);
                 if (at.on) D.rd[D.at(at.off, bt_chain(NP, wg, si * 16 + (lane & 15)), pos + 1, -1, -1, true, wg, lane)]++;
                 const BtAt it = bt_img_tile(n, NP, lane, si, sj, r);
-                if (it.on != (bt_next_at({ldd, step_d, stride_d, pos + 2, bt_chain(NP, wg, 63) + 1, n, NP}, wg, lane, pos, si, sj, r).on))
+                const BtGeo all = {ldd, step_d, stride_d, pos + 2, bt_chain(NP, wg, 63) + 1, n, NP};      // every group alive, with a successor
+                if (it.on != bt_next_at(all, bt_chain_fixed(all, all, 0, wg, bt_row_group(NP, lane, si)), lane, pos, si, sj, r).on)
                   fail("image", "the tile store and the tile load disagree", it.off, wg, lane, pos);
                 if (it.on && has) { lds(it.off, img, "image", wg, lane, pos); imgw[(size_t)it.off]++; }
               }
@@ -134,12 +141,12 @@ int main() {
             lds(bt_img_base(NP, lane) + (i <= lane % NP ? bt_img_at(NP, i, lane % NP) : bt_img_at(NP, lane % NP, i)), img, "image", wg, lane, pos);
           lds(bt_log_at(NP, lane, lane % NP), 64, "logarithms", wg, lane, pos);
           for (int cc = 0; cc < n; cc++) {         // U_pos -> D_pos
-            const BtAt at = bt_tri_at(gd, wg, lane, pos, cc);
+            const BtAt at = bt_tri_at(gd, own, lane, pos, cc);
             if (at.on) D.wr[D.at(at.off, chain, pos, lane % NP, cc, true, wg, lane)]++;
           }
           if (!has) continue;
           for (int i = 0; i < n; i++) {            // W_pos -> E_pos and the exchange area
-            const BtAt at = bt_ecol_at(ge, wg, lane, pos, i);
+            const BtAt at = bt_ecol_at(ge, own, lane, pos, i);
             if (at.on) E.wr[E.at(at.off, chain, pos, i, lane % NP, false, wg, lane)]++;
             lds(bt_x_own(i, lane), xs, "exchange", wg, lane, pos);
           }
@@ -157,7 +164,7 @@ int main() {
                 if (imgw[(size_t)(grp * bt_img_size(NP) + bt_img_at(NP, r, c))] != 1) fail("image", "an element of the successor is not written once", r + c * n, wg, grp, pos);
       }
       for (int lane = 0; lane < 64; lane++) {
-        const BtAt at = bt_scalar_at(gd, wg, lane);
+        const BtAt at = bt_scalar_at(NP, own_of(wg, lane), lane);
         if (at.on) {
           if (at.off < 0 || at.off >= batch || at.off != bt_chain(NP, wg, lane)) fail("info", "not the chain's entry", at.off, wg, lane, -1);
           scalars[(size_t)at.off]++;
@@ -181,32 +188,46 @@ int main() {
       std::fill(D.rd.begin(), D.rd.end(), 0);
       if (eblocks > 0) std::fill(E.rd.begin(), E.rd.end(), 0);
       const long long passes = bt_rhs_passes(NP, nrhs);
-      auto seg = [&](std::vector<int>& v, long long wg, long long pass, long long pos) {
-        for (int lane = 0; lane < 64; lane++)
+      // a step of a sweep: ascending at position `step`, descending at T - 1 - step of the addressed chain (bt_pos); the walk has T steps
+      auto seg = [&](std::vector<int>& v, long long wg, long long pass, long long step, bool desc, bool target) {
+        for (int lane = 0; lane < 64; lane++) {
+          const BtChain own = own_of(wg, lane);
+          const long long pos = target ? bt_couple_tpos(own, step, desc) : bt_pos(own, step, desc);
           for (int i = 0; i < n; i++) {
-            const BtAt at = bt_rhs_at(gd, ldb, stride_b, nrhs, wg, lane, pass, pos, i);
+            const BtAt at = bt_rhs_at(gd, own, ldb, nrhs, lane, pass, pos, i);
             if (at.on) v[B.at(at.off, bt_chain(NP, wg, lane), pass * NP + lane % NP, pos * n + i, wg, lane)]++;
           }
+        }
       };
-      auto tri = [&](long long wg, long long pos) {
-        for (int lane = 0; lane < 64; lane++)
+      auto tri = [&](long long wg, long long step, bool desc) {
+        for (int lane = 0; lane < 64; lane++) {
+          const BtChain own = own_of(wg, lane);
+          const long long pos = bt_pos(own, step, desc);
+          if (own.T > 0 && pos != (desc ? T - 1 - step : step)) fail("D", "the walk is not at the step's position", pos, wg, lane, step);
           for (int cc = 0; cc < n; cc++) {
-            const BtAt at = bt_tri_at(gd, wg, lane, pos, cc);
+            const BtAt at = bt_tri_at(gd, own, lane, pos, cc);
             if (at.on) D.rd[D.at(at.off, bt_chain(NP, wg, lane), pos, lane % NP, cc, true, wg, lane)]++;
           }
+        }
       };
-      auto couple = [&](long long wg, long long pass, long long epos, long long tpos, bool trans) {
-        seg(B.rd, wg, pass, tpos);
+      auto couple = [&](long long wg, long long pass, long long step, bool desc) {
+        const long long epos = desc ? T - 2 - step : step, tpos = desc ? T - 2 - step : step + 1;      // of every chain that is alive
+        const bool trans = !desc;
+        seg(B.rd, wg, pass, step, desc, true);
         std::vector<int> xw((size_t)xs, 0);
         bool onc[4];
         for (int sl = 0; sl < 4; sl++) onc[sl] = pass * NP + (sl * 16) % NP < nrhs;
         for (int lane = 0; lane < 64; lane++) {
-          if (bt_rhs_at(gd, ldb, stride_b, nrhs, wg, lane, pass, tpos, 0).on && !onc[lane / 16]) fail("exchange", "a live column in a skipped slab", lane, wg, lane, tpos);
+          const BtChain own = own_of(wg, lane);
+          if (own.T > 0 && bt_couple_tpos(own, step, desc) != tpos) fail("B", "not the target segment of the step", tpos, wg, lane, step);
+          if (bt_rhs_at(gd, own, ldb, nrhs, lane, pass, bt_couple_tpos(own, step, desc), 0).on && !onc[lane / 16]) fail("exchange", "a live column in a skipped slab", lane, wg, lane, tpos);
           for (int i = 0; i < n; i++) lds(bt_x_own(i, lane), xs, "exchange", wg, lane, tpos);
           for (int q = 0; q < n; q += 4)
             for (int sl = 0; sl < 4; sl++) {
               if (bt_slab_on(NP, sl, n)) {
-                const BtAt at = bt_eslab_at(ge, wg, lane, epos, sl, q, trans);
+                const BtChain chr = row_of(wg, lane, sl);
+                if (chr.T > 0 && bt_couple_epos(chr, step, desc) != epos) fail("E", "not the coupling block of the step", epos, wg, lane, step);
+                const BtAt at = bt_eslab_at(ge, chr, lane, bt_couple_epos(chr, step, desc), sl, q, trans);
                 const int row = (sl * 16 + lane % 16) % NP, k = q + lane / 16;
                 if (at.on) E.rd[E.at(at.off, bt_chain(NP, wg, sl * 16 + lane % 16), epos, trans ? k : row, trans ? row : k, false, wg, lane)]++;
               }
@@ -229,29 +250,20 @@ int main() {
       };
       for (long long wg = 0; wg < nwg; wg++) {
         for (int lane = 0; lane < 64; lane++) {
-          const BtAt at = bt_info_at(gd, wg, lane);
+          const BtAt at = bt_info_at(own_of(wg, lane));
           if (at.on && (at.off >= batch || at.off != bt_chain(NP, wg, lane))) fail("info", "not the chain's entry", at.off, wg, lane, -1);
         }
-        for (long long pass = 0; pass < passes; pass++) {
-          if (half != 2) {
-            seg(B.rd, wg, pass, 0);
-            for (long long pos = 0; pos < T; pos++) {
-              tri(wg, pos);
-              seg(B.wr, wg, pass, pos);
-              if (!bt_has_next(T, pos)) break;
-              couple(wg, pass, pos, pos + 1, true);
+        for (long long pass = 0; pass < passes; pass++)
+          for (int desc = 0; desc < 2; desc++) {
+            if ((desc == 0 && half == 2) || (desc == 1 && half == 1)) continue;
+            seg(B.rd, wg, pass, 0, desc != 0, false);
+            for (long long step = 0; step < T; step++) {
+              tri(wg, step, desc != 0);
+              seg(B.wr, wg, pass, step, desc != 0, false);
+              if (!bt_has_next(T, step)) break;
+              couple(wg, pass, step, desc != 0);
             }
           }
-          if (half != 1) {
-            seg(B.rd, wg, pass, T - 1);
-            for (long long pos = T - 1; pos >= 0; pos--) {
-              tri(wg, pos);
-              seg(B.wr, wg, pass, pos);
-              if (pos == 0) break;
-              couple(wg, pass, pos - 1, pos - 1, false);
-            }
-          }
-        }
       }
       const int sweeps = half == 0 ? 2 : 1;
       for (size_t e = 0; e < B.wr.size(); e++)

@@ -1,4 +1,5 @@
-// TEST INFRASTRUCTURE of tests/test_blocktri_potri_addr.py: the loops of capital_amd/csrc/blocktri_potri_batched.hip (blocktri_potri_kernel)
+// TEST INFRASTRUCTURE of tests/test_blocktri_potri_addr.py: the loops of bt_inverse (capital_amd/csrc/blocktri_kernels.h) as
+// blocktri_potri_batched.hip launches them - the chain of a lane group from bt_chain_fixed, a walk of T steps at position T - 1 - step -
 // replayed on the CPU, workgroup by workgroup and lane by lane, with the address functions the kernel itself calls
 // (capital_amd/csrc/blocktri_addr.h).  Reads one launch per line from stdin:
 //   n T batch fill ldd step_d stride_d lde step_e stride_e eblocks dfirst
@@ -82,6 +83,9 @@ int main() {
     D.init();
     E.init();
     const long long img = (long long)G * bt_img_size(NP), xs = bt_x_size(NP);
+    // the chain of a lane (its own group's) and of its wave row in slab s, as BtFixed answers
+    auto own_of = [&](long long wg, int lane) { return bt_chain_fixed(gd, ge, 0, wg, bt_group(NP, lane)); };
+    auto row_of = [&](const BtGeo& g, long long wg, int lane, int s) { return bt_chain_fixed(g, g, 0, wg, bt_row_group(NP, lane, s)); };
 
     for (long long wg = 0; wg < nwg; wg++) {
       std::vector<int> gw((size_t)xs, 0), sw((size_t)xs, 0), cleared((size_t)(2 * xs), 0);
@@ -94,7 +98,7 @@ int main() {
         if (v != 1) fail("exchange", "a word is not cleared once", v, wg, -1, -1);
       for (int lane = 0; lane < 64; lane++)
         for (int cc = 0; cc < n; cc++) {
-          const BtAt at = bt_tri_at(gd, wg, lane, bt_walk_pos(T, 0), cc);
+          const BtAt at = bt_tri_at(gd, own_of(wg, lane), lane, bt_pos(own_of(wg, lane), 0, true), cc);
           if (at.on) {
             D.rd[D.at(at.off, bt_chain(NP, wg, lane), T - 1, lane % NP, cc, true, wg, lane)]++;
             lds(bt_img_base(NP, lane) + bt_img_at(NP, lane % NP, cc), img, "image", wg, lane, T - 1);
@@ -122,23 +126,28 @@ int main() {
 
       auto ecol = [&](long long wg_, int lane, long long p, bool may) {
         for (int i = 0; i < n; i++) {
-          const BtAt at = bt_ecol_at(ge, wg_, lane, p, i);
+          const BtAt at = bt_ecol_at(ge, own_of(wg_, lane), lane, p, i);
           if (at.on && !may) fail("E", "a coupling block at position -1", at.off, wg_, lane, p);
           if (at.on) E.rd[E.at(at.off, bt_chain(NP, wg_, lane), p, i, lane % NP, false, wg_, lane)]++;
         }
       };
       auto tri = [&](long long wg_, int lane, long long p, bool may) {
         for (int cc = 0; cc < n; cc++) {
-          const BtAt at = bt_tri_at(gd, wg_, lane, p, cc);
+          const BtAt at = bt_tri_at(gd, own_of(wg_, lane), lane, p, cc);
           if (at.on && !may) fail("D", "a predecessor at position 0", at.off, wg_, lane, p);
           if (at.on) D.rd[D.at(at.off, bt_chain(NP, wg_, lane), p, lane % NP, cc, true, wg_, lane)]++;
         }
       };
 
       for (long long step = 0; step < T; step++) {
-        const long long pos = bt_walk_pos(T, step);
-        const bool first = step == 0, prev = bt_has_prev(pos);
-        if (pos < 0 || pos >= T) fail("D", "the walk leaves the chain", pos, wg, -1, pos);
+        const long long pos = T - 1 - step;          // of every chain that is alive
+        const bool first = step == 0, prev = bt_has_next(T, step);       // the kernel's wave-uniform test: the walk goes on
+        if (pos < 0 || pos >= T || prev != (pos > 0)) fail("D", "the walk leaves the chain", pos, wg, -1, pos);
+        for (int lane = 0; lane < 64; lane++) {
+          const BtChain own = own_of(wg, lane);
+          if (own.T != (bt_chain(NP, wg, lane) < batch ? T : 0) || own.id != bt_chain(NP, wg, lane)) fail("chain", "not the lane group's chain", own.id, wg, lane, pos);
+          if (own.T > 0 && bt_pos(own, step, true) != pos) fail("D", "the walk is not at the step's position", bt_pos(own, step, true), wg, lane, pos);
+        }
         // the requests, as the kernel makes them: row r of U_(pos-1) in front of position pos at NP <= 32 (position 0 included: the answer
         // must be off), behind it otherwise; column c of E_(pos-1) behind the substitution of every position but the first at NP < 64
         // (the first one of a chain in front of the walk), column c of E_pos in front of it at NP = 64
@@ -165,10 +174,11 @@ int main() {
                 for (int r = 0; r < 4; r++) {
                   if (!bt_tile(NP, si, sj, false) || !bt_slab_on(NP, si, n) || !bt_slab_on(NP, sj, n)) continue;
                   const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
-                  const BtAt at = bt_etile_at(ge, wg, lane, pos, si, sj, r);
+                  const BtChain chr = row_of(ge, wg, lane, si);
+                  const BtAt at = bt_etile_at(ge, chr, lane, bt_pos(chr, step, true), si, sj, r);
                   if (at.on) E.wr[E.at(at.off, bt_chain(NP, wg, wi), pos, wi % NP, wj % NP, false, wg, lane)]++;
                   const BtAt xt = bt_xt_tile(n, NP, lane, si, sj, r);
-                  if (xt.on != bt_etile_at(all, wg, lane, pos, si, sj, r).on) fail("exchange", "the tile store of C and its copy in LDS disagree", xt.off, wg, lane, pos);
+                  if (xt.on != bt_etile_at(all, row_of(all, wg, lane, si), lane, pos, si, sj, r).on) fail("exchange", "the tile store of C and its copy in LDS disagree", xt.off, wg, lane, pos);
                   if (xt.on) {
                     lds(xt.off, xs, "exchange", wg, lane, pos);
                     if (xt.off != bt_x_own(wj % NP, wi)) fail("exchange", "not word wi of line col", xt.off, wg, lane, pos);
@@ -178,7 +188,7 @@ int main() {
           product(sw, gw, "C", "G", true, pos);
         } else {                                   // position T - 1: the kernel asks for no coupling block; the accessor would say no
           for (int lane = 0; lane < 64; lane++)
-            if (bt_etile_at(ge, wg, lane, pos, 0, 0, 0).on || bt_ecol_at(ge, wg, lane, pos, 0).on) fail("E", "a coupling block at position T - 1", 0, wg, lane, pos);
+            if (bt_etile_at(ge, row_of(ge, wg, lane, 0), lane, pos, 0, 0, 0).on || bt_ecol_at(ge, own_of(wg, lane), lane, pos, 0).on) fail("E", "a coupling block at position T - 1", 0, wg, lane, pos);
         }
         std::vector<int> seen((size_t)img, 0);
         std::fill(sw.begin(), sw.end(), 0);
@@ -202,7 +212,7 @@ int main() {
             }
         for (int lane = 0; lane < 64; lane++)      // Sigma -> D_pos
           for (int cc = 0; cc < n; cc++) {
-            const BtAt at = bt_full_at(gd, wg, lane, pos, cc, fill);
+            const BtAt at = bt_full_at(gd, own_of(wg, lane), lane, pos, cc, fill);
             if (!at.on) continue;
             D.wr[D.at(at.off, bt_chain(NP, wg, lane), pos, lane % NP, cc, fill == 0, wg, lane)]++;
             lds(bt_x_own(cc, lane), xs, "exchange", wg, lane, pos);

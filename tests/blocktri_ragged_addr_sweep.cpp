@@ -1,7 +1,7 @@
-// TEST INFRASTRUCTURE of tests/test_blocktri_ragged_addr.py: the loops of capital_amd/csrc/blocktri_vbatched.hip (blocktri_vpotrf_kernel,
-// blocktri_vpotrs_kernel with half = 0, 1, 2, blocktri_vpotri_kernel with fill = 0, 1) replayed on the CPU, workgroup by workgroup and
-// lane by lane over the plan's sorted list, with the address functions the kernels themselves call (capital_amd/csrc/blocktri_addr.h, the
-// btv_ section) and asked exactly as the kernels ask them, the prefetches included.  Reads one launch per line from stdin:
+// TEST INFRASTRUCTURE of tests/test_blocktri_ragged_addr.py: the loops of capital_amd/csrc/blocktri_kernels.h (bt_factor, bt_solve with
+// half = 0, 1, 2, bt_inverse with fill = 0, 1) as blocktri_vbatched.hip launches them - the chain of a lane group from bt_chain_plan -
+// replayed on the CPU, workgroup by workgroup and lane by lane over the plan's sorted list, with the address functions the kernels
+// themselves call (capital_amd/csrc/blocktri_addr.h) and asked exactly as the kernels ask them, the prefetches included.  Reads one launch per line from stdin:
 //   n nrhs ldd step_d lde step_e ldb eslots batch  then per chain: T first R
 // T and first are what the PLAN says; R is the number of positions the chain's operands really hold and eslots the number of slots the E
 // operand really holds - R = T and eslots = the plan's ESLOTS for every launch the library makes; a line that says less is a planted fault.
@@ -143,15 +143,15 @@ int main() {
     const long long img = (long long)G * bt_img_size(NP), xs = bt_x_size(NP);
     long long phase = 0;
 
-    // the wavefront's table, as bv_lookup fills it: a group beyond the list has T = 0 (its id is never used)
+    // the wavefront's table, as BtPlan fills it: a group beyond the list has T = 0 (its id is never used)
     auto table = [&](long long wg, BtChain* tab, long long& Tw) {
       Tw = 0;
       for (int grp = 0; grp < G; grp++) {
         const long long at = bt_chain(NP, wg, grp * NP);
-        tab[grp] = BtChain{0, 0, 0, -1};
+        tab[grp] = bt_chain_plan(gd, ge, 0, 0, 0, -1);
         if (at < batch) {
           const long long id = order[(size_t)at];
-          tab[grp] = BtChain{ch[(size_t)id].first, ch[(size_t)id].T, ch[(size_t)id].row, id};
+          tab[grp] = bt_chain_plan(gd, ge, ch[(size_t)id].first, ch[(size_t)id].T, ch[(size_t)id].row, id);
         }
         Tw = std::max(Tw, (long long)tab[grp].T);
       }
@@ -166,7 +166,7 @@ int main() {
       for (int lane = 0; lane < 64; lane++)
         for (int cc = 0; cc < n; cc++) {
           const BtChain& own = tab[bt_group(NP, lane)];
-          const BtAt at = btv_tri_at(gd, own, lane, 0, cc);
+          const BtAt at = bt_tri_at(gd, own, lane, 0, cc);
           if (at.on) { D.rd[D.at(at.off, own.id, 0, lane % NP, cc, true, wg, lane)]++; lds(bt_img_base(NP, lane) + bt_img_at(NP, lane % NP, cc), img, "image", wg, lane, 0); }
         }
       Area X;
@@ -176,15 +176,15 @@ int main() {
         for (int lane = 0; lane < 64; lane++) {
           const BtChain& own = tab[bt_group(NP, lane)];
           for (int i = 0; i < n; i++) {            // the request for E_pos: asked at every step
-            const BtAt at = btv_ecol_at(ge, own, lane, pos, i);
+            const BtAt at = bt_ecol_at(ge, own, lane, pos, i);
             if (at.on) E.rd[E.at(at.off, own.id, pos, i, lane % NP, false, wg, lane)]++;
           }
           for (int si = 0; si < 4; si++) {         // the request for D_(pos+1), asked about the chain of the wave row
-            const BtChain& chr = tab[btv_row_group(NP, lane, si)];
+            const BtChain& chr = tab[bt_row_group(NP, lane, si)];
             for (int sj = 0; sj < 4; sj++)
               for (int r = 0; r < 4; r++) {
                 if (!bt_tile(NP, si, sj, true) || !bt_slab_on(NP, si, n) || !bt_slab_on(NP, sj, n)) continue;
-                const BtAt at = btv_next_at(gd, chr, lane, pos, si, sj, r);
+                const BtAt at = bt_next_at(gd, chr, lane, pos, si, sj, r);
                 const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
                 if (at.on) D.rd[D.at(at.off, chr.id, pos + 1, wi % NP, wj % NP, true, wg, lane)]++;
                 const BtAt it = bt_img_tile(n, NP, lane, si, sj, r);
@@ -193,7 +193,7 @@ int main() {
               }
           }
           for (int cc = 0; cc < n; cc++) {         // U_pos -> D_pos
-            const BtAt at = btv_tri_at(gd, own, lane, pos, cc);
+            const BtAt at = bt_tri_at(gd, own, lane, pos, cc);
             if (at.on) D.wr[D.at(at.off, own.id, pos, lane % NP, cc, true, wg, lane)]++;
           }
           lds(bt_log_at(NP, lane, lane % NP), 64, "logarithms", wg, lane, pos);
@@ -202,7 +202,7 @@ int main() {
         for (int lane = 0; lane < 64; lane++) {
           const BtChain& own = tab[bt_group(NP, lane)];
           for (int i = 0; i < n; i++) {            // W_pos -> E_pos and, for every lane, the exchange area (+0.0 where the lane has none)
-            const BtAt at = btv_ecol_at(ge, own, lane, pos, i);
+            const BtAt at = bt_ecol_at(ge, own, lane, pos, i);
             if (at.on) E.wr[E.at(at.off, own.id, pos, i, lane % NP, false, wg, lane)]++;
             X.write(bt_x_own(i, lane), phase, wg, lane, pos);
           }
@@ -217,7 +217,7 @@ int main() {
       }
       for (int lane = 0; lane < 64; lane++) {
         const BtChain& own = tab[bt_group(NP, lane)];
-        const BtAt at = btv_scalar_at(NP, own, lane);
+        const BtAt at = bt_scalar_at(NP, own, lane);
         if (at.on) {
           if (at.off < 0 || at.off >= batch || ch[(size_t)at.off].T == 0) fail("info", "not the entry of a chain with a position", at.off, wg, lane, -1);
           scalars[(size_t)at.off]++;
@@ -244,7 +244,7 @@ int main() {
         long long Tw;
         table(wg, tab, Tw);
         for (int lane = 0; lane < 64; lane++) {
-          const BtAt at = btv_info_at(tab[bt_group(NP, lane)]);
+          const BtAt at = bt_info_at(tab[bt_group(NP, lane)]);
           if (at.on && (at.off < 0 || at.off >= batch || ch[(size_t)at.off].T == 0)) fail("info", "not the entry of a chain with a position", at.off, wg, lane, -1);
         }
         Area X;
@@ -252,9 +252,9 @@ int main() {
         auto seg = [&](std::vector<int>& v, long long pass, long long step, bool desc, bool target) {
           for (int lane = 0; lane < 64; lane++) {
             const BtChain& own = tab[bt_group(NP, lane)];
-            const long long pos = target ? btv_couple_tpos(own, step, desc) : btv_pos(own, step, desc);
+            const long long pos = target ? bt_couple_tpos(own, step, desc) : bt_pos(own, step, desc);
             for (int i = 0; i < n; i++) {
-              const BtAt at = btv_rhs_at(gd, own, ldb, nrhs, lane, pass, pos, i);
+              const BtAt at = bt_rhs_at(gd, own, ldb, nrhs, lane, pass, pos, i);
               if (at.on) v[B.at(at.off, own.id, pass * NP + lane % NP, pos, i, wg, lane)]++;
             }
           }
@@ -262,9 +262,9 @@ int main() {
         auto tri = [&](long long step, bool desc) {
           for (int lane = 0; lane < 64; lane++) {
             const BtChain& own = tab[bt_group(NP, lane)];
-            const long long pos = btv_pos(own, step, desc);
+            const long long pos = bt_pos(own, step, desc);
             for (int cc = 0; cc < n; cc++) {
-              const BtAt at = btv_tri_at(gd, own, lane, pos, cc);
+              const BtAt at = bt_tri_at(gd, own, lane, pos, cc);
               if (at.on) D.rd[D.at(at.off, own.id, pos, lane % NP, cc, true, wg, lane)]++;
             }
           }
@@ -279,13 +279,13 @@ int main() {
           std::vector<int> xw((size_t)xs, 0);
           for (int lane = 0; lane < 64; lane++) {
             const BtChain& own = tab[bt_group(NP, lane)];
-            if (btv_rhs_at(gd, own, ldb, nrhs, lane, pass, btv_couple_tpos(own, step, desc), 0).on && !onc[lane / 16]) fail("exchange", "a live column in a skipped slab", lane, wg, lane, step);
+            if (bt_rhs_at(gd, own, ldb, nrhs, lane, pass, bt_couple_tpos(own, step, desc), 0).on && !onc[lane / 16]) fail("exchange", "a live column in a skipped slab", lane, wg, lane, step);
             for (int q = 0; q < n; q += 4)
               for (int sl = 0; sl < 4; sl++) {
                 if (bt_slab_on(NP, sl, n)) {
-                  const BtChain& chr = tab[btv_row_group(NP, lane, sl)];
-                  const long long epos = btv_couple_epos(chr, step, desc);
-                  const BtAt at = btv_eslab_at(ge, chr, lane, epos, sl, q, !desc);
+                  const BtChain& chr = tab[bt_row_group(NP, lane, sl)];
+                  const long long epos = bt_couple_epos(chr, step, desc);
+                  const BtAt at = bt_eslab_at(ge, chr, lane, epos, sl, q, !desc);
                   const int row = (sl * 16 + lane % 16) % NP, k = q + lane / 16;
                   if (at.on) E.rd[E.at(at.off, chr.id, epos, !desc ? k : row, !desc ? row : k, false, wg, lane)]++;
                 }
@@ -350,14 +350,14 @@ int main() {
         auto tri_read = [&](int lane, long long pos) {
           const BtChain& own = tab[bt_group(NP, lane)];
           for (int cc = 0; cc < n; cc++) {
-            const BtAt at = btv_tri_at(gd, own, lane, pos, cc);
+            const BtAt at = bt_tri_at(gd, own, lane, pos, cc);
             if (at.on) D.rd[D.at(at.off, own.id, pos, lane % NP, cc, true, wg, lane)]++;
           }
         };
         auto ecol_read = [&](int lane, long long pos) {
           const BtChain& own = tab[bt_group(NP, lane)];
           for (int i = 0; i < n; i++) {
-            const BtAt at = btv_ecol_at(ge, own, lane, pos, i);
+            const BtAt at = bt_ecol_at(ge, own, lane, pos, i);
             if (at.on) E.rd[E.at(at.off, own.id, pos, i, lane % NP, false, wg, lane)]++;
           }
         };
@@ -374,8 +374,8 @@ int main() {
         };
         for (int lane = 0; lane < 64; lane++) {
           const BtChain& own = tab[bt_group(NP, lane)];
-          tri_read(lane, btv_pos(own, 0, true));
-          if (EARLY) ecol_read(lane, btv_pos(own, 0, true) - 1);
+          tri_read(lane, bt_pos(own, 0, true));
+          if (EARLY) ecol_read(lane, bt_pos(own, 0, true) - 1);
         }
         long long sig_phase = -2;
         for (long long step = 0; step < Tw; step++) {
@@ -383,7 +383,7 @@ int main() {
           const long long pg = ++phase;
           for (int lane = 0; lane < 64; lane++) {
             const BtChain& own = tab[bt_group(NP, lane)];
-            const long long pos = btv_pos(own, step, true);
+            const long long pos = bt_pos(own, step, true);
             if (EARLY_U) tri_read(lane, pos - 1);
             if (!first) {
               if (!EARLY) ecol_read(lane, pos);
@@ -397,13 +397,13 @@ int main() {
             const long long pc = ++phase;
             for (int lane = 0; lane < 64; lane++)
               for (int si = 0; si < 4; si++) {
-                const BtChain& chr = tab[btv_row_group(NP, lane, si)];
-                const long long rpos = btv_pos(chr, step, true);
+                const BtChain& chr = tab[bt_row_group(NP, lane, si)];
+                const long long rpos = bt_pos(chr, step, true);
                 for (int sj = 0; sj < 4; sj++)
                   for (int r = 0; r < 4; r++) {
                     if (!bt_tile(NP, si, sj, false) || !bt_slab_on(NP, si, n) || !bt_slab_on(NP, sj, n)) continue;
                     const int wi = si * 16 + (lane & 15), wj = sj * 16 + (lane >> 4) + 4 * r;
-                    const BtAt at = btv_etile_at(ge, chr, lane, rpos, si, sj, r);
+                    const BtAt at = bt_etile_at(ge, chr, lane, rpos, si, sj, r);
                     if (at.on) E.wr[E.at(at.off, chr.id, rpos, wi % NP, wj % NP, false, wg, lane)]++;
                     const BtAt xt = bt_xt_tile(n, NP, lane, si, sj, r);
                     if (xt.on) { below_n(xt.off, "exchange X2", wg, lane, step); XS.write(xt.off, pc, wg, lane, step); }
@@ -426,15 +426,15 @@ int main() {
                 }
           for (int lane = 0; lane < 64; lane++) {
             const BtChain& own = tab[bt_group(NP, lane)];
-            const long long pos = btv_pos(own, step, true);
+            const long long pos = bt_pos(own, step, true);
             for (int cc = 0; cc < n; cc++) {
-              const BtAt at = btv_full_at(gd, own, lane, pos, cc, fill);
+              const BtAt at = bt_full_at(gd, own, lane, pos, cc, fill);
               if (at.on) { D.wr[D.at(at.off, own.id, pos, lane % NP, cc, fill == 0, wg, lane)]++; XS.read(bt_x_own(cc, lane), sig_phase, wg, lane, step); }
             }
           }
           if (!bt_has_next(Tw, step)) break;
           if (!EARLY_U)
-            for (int lane = 0; lane < 64; lane++) tri_read(lane, btv_pos(tab[bt_group(NP, lane)], step, true) - 1);
+            for (int lane = 0; lane < 64; lane++) tri_read(lane, bt_pos(tab[bt_group(NP, lane)], step, true) - 1);
         }
       }
       D.expect(D.rd, 1, true, "the inverse does not read the factor's element exactly once");

@@ -1,4 +1,4 @@
-"""CPU-only: the address arithmetic of the ragged block-tridiagonal kernels (the btv_ section of capital_amd/csrc/blocktri_addr.h) swept
+"""CPU-only: the address arithmetic of the ragged block-tridiagonal kernels (capital_amd/csrc/blocktri_addr.h on bt_chain_plan chains) swept
 workgroup by workgroup and lane by lane by a stand-alone C++ program (tests/blocktri_ragged_addr_sweep.cpp, built here with g++ and the
 address and undefined-behaviour sanitizers) over every row of tests/blocktri_ragged_cases.py, on the plan's sorted order: the factor, the
 solve with half = 0, 1, 2 and the selected inverse with fill = 0, 1.  Every offset must lie inside the addressed chain's OWN slots of D

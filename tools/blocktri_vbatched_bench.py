@@ -12,11 +12,17 @@ log-uniform on [1, T_max], "mostly short" (95 % at T_max / 16, the rest at T_max
 Then all lengths equal (the plan against the fixed-size entry on the same data: what the record lookup and the activity predicates cost,
 per NP) and the few-long-chains corner (64 chains around 10000 positions, n = 8: microseconds per position).
 The calls work in place, so every window of the factor and the inverse starts with a restoring copy; its own time is reported (the
-floor) and is part of every figure of that row, ours and the other routes' alike.  Writes the table to --out and prints it:
+floor) and is part of every figure of that row, ours and the other routes' alike.
+With --parent-lib: the six entries (factor, solve, inverse; fixed size and on a plan) of this build and of another build of the library
+(the parent commit's) through the C ABI, alternating in this process on the "all lengths equal" shapes; per row the ratio this / parent
+without the restoring copy, held against 1 + max(0.02, the parent's own spread (slowest - fastest) / median in this run).
+--sections picks what is run.  Writes the table to --out and prints it:
 
     timeout -k 10 900 python tools/blocktri_vbatched_bench.py [--reps 9] [--out profiles/r31_blocktri_vbatched.txt]
+                                                              [--sections ragged,equal,long,parent] [--parent-lib path/to/libcapital_amd.so]
 """
 import argparse
+import ctypes as C
 import os
 import sys
 
@@ -26,7 +32,7 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from capital_amd import batched, build  # noqa: E402
+from capital_amd import _lib, batched, build  # noqa: E402
 from tools.blocktri_bench import fmt, run  # noqa: E402
 
 SHAPES = ((8, 256, 4096), (16, 128, 4096), (32, 64, 2048), (64, 32, 1024))
@@ -178,27 +184,95 @@ def long_section(reps, rng):
     say()
 
 
+ENTRIES = ("cap_dpotrf_blocktri_batched", "cap_dpotrs_blocktri_batched", "cap_dpotri_blocktri_batched", "cap_blocktri_plan_create",
+           "cap_blocktri_plan_destroy", "cap_dpotrf_blocktri_vbatched", "cap_dpotrs_blocktri_vbatched", "cap_dpotri_blocktri_vbatched")
+
+
+def parent_section(n, T, batch, reps, libs):
+    """the six entries of both libraries on one set of buffers (a plan of each library's own); False when a row does not hold"""
+    D, E = slots_of(n, batch * T, n * 1000 + T)                # slot c T + i: block i of chain c; the last E slot of a chain is not addressed
+    B = torch.rand(NRHS, batch * T * n, dtype=torch.float64, device="cuda")
+    B3 = torch.rand(batch, NRHS, T * n, dtype=torch.float64, device="cuda")
+    info = torch.zeros(batch, dtype=torch.int32, device="cuda")
+    sp = torch.cuda.current_stream().cuda_stream
+    d, e, b, b3, ip, nn, chain = D.data_ptr(), E.data_ptr(), B.data_ptr(), B3.data_ptr(), info.data_ptr(), n * n, T * n * n
+    plans = {}
+    for tag, lib in libs.items():
+        plans[tag] = C.c_void_p()
+        _lib.check(lib.cap_blocktri_plan_create(batch, (C.c_int64 * batch)(*([T] * batch)), None, C.byref(plans[tag])), "cap_blocktri_plan_create")
+    calls = {
+        "fixed factor": lambda lib, p: lib.cap_dpotrf_blocktri_batched(1, n, T, d, n, nn, chain, e, n, nn, chain, ip, None, batch, sp),
+        "plan  factor": lambda lib, p: lib.cap_dpotrf_blocktri_vbatched(p, 1, n, d, n, nn, e, n, nn, ip, None, sp),
+        "fixed solve": lambda lib, p: lib.cap_dpotrs_blocktri_batched(1, 0, n, T, NRHS, d, n, nn, chain, e, n, nn, chain, b3, T * n, NRHS * T * n, None, batch, sp),
+        "plan  solve": lambda lib, p: lib.cap_dpotrs_blocktri_vbatched(p, 1, 0, n, NRHS, d, n, nn, e, n, nn, b, batch * T * n, None, sp),
+        "fixed inverse": lambda lib, p: lib.cap_dpotri_blocktri_batched(1, 0, n, T, d, n, nn, chain, e, n, nn, chain, None, batch, sp),
+        "plan  inverse": lambda lib, p: lib.cap_dpotri_blocktri_vbatched(p, 1, 0, n, d, n, nn, e, n, nn, None, sp),
+    }
+    sd, sb = Store(D, E), Store(B, B3)
+    sd(); _lib.check(calls["fixed factor"](libs["this"], None)); keep = sd.snapshot()      # the factor, for the solve and the inverse
+    say("n = %d (NP = %d), T = %d, %d chains: this build and the parent's, alternating" % (n, 8 if n <= 8 else 16 if n <= 16 else 32 if n <= 32 else 64, T, batch))
+    say("  %-14s %-32s %-32s %-32s %8s %8s %s" % ("entry", "this + copy", "parent + copy", "copy (floor)", "this/par", "1 + s", "holds"))
+    good = True
+    for name, call in calls.items():
+        restore = sb if "solve" in name else sd if "factor" in name else keep
+        r = run([("floor", restore)] + [(tag, lambda lib=lib, tag=tag: (restore(), _lib.check(call(lib, plans[tag])))) for tag, lib in libs.items()], reps)
+        x, y, fl = r["this"], r["parent"], r["floor"]
+        ratio, bound = (x[0] - fl[0]) / (y[0] - fl[0]), 1.0 + max(0.02, (y[2] - y[1]) / y[0])
+        good = good and ratio <= bound
+        say("  %-14s %s %s %s %8.3f %8.3f %s" % (name, fmt(x), fmt(y), fmt(fl), ratio, bound, "yes" if ratio <= bound else "NO"))
+    say()
+    for tag, lib in libs.items():
+        lib.cap_blocktri_plan_destroy(plans[tag])
+    del D, E, B, B3, sd, sb, keep
+    torch.cuda.empty_cache()
+    return good
+
+
+def resources():
+    say("kernel resources (the compiler's remarks of this build):")
+    for name, v in sorted(build.kernel_resources().items()):
+        if "blocktri_" in name:
+            say("  %-84s VGPRs %3s  AGPRs %3s  LDS %6s  scratch %s  spilled %s  waves/SIMD %s"
+                % (name, v.get("VGPRs"), v.get("AGPRs"), v.get("LDS Size"), v.get("ScratchSize"), v.get("VGPRs Spill"), v.get("Occupancy")))
+    say()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
+    ap.add_argument("--sections", default="ragged,equal,long,parent")
+    ap.add_argument("--parent-lib", default=None)
+    ap.add_argument("--title", default="Ragged block-tridiagonal chains on a plan (csrc/blocktri_vbatched.hip) - round 31")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r31_blocktri_vbatched.txt"))
     a = ap.parse_args()
     build.build(verbose=False)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     OUT[0] = open(a.out, "w")
-    say("Ragged block-tridiagonal chains on a plan (csrc/blocktri_vbatched.hip) - round 31")
+    sections = a.sections.split(",")
+    say(a.title)
     say("tools/blocktri_vbatched_bench.py on one %s, torch %s, ONE run, median [fastest slowest] of %d windows after a warm-up round, times in ms per call"
         % (torch.cuda.get_device_name(0), torch.__version__, a.reps))
     say("device text (md5 of the gfx950 .text of the last build): " + ", ".join("%s %s" % (s, build.device_text_md5(s)) for s in (
         "blocktri_batched.hip", "blocktri_potri_batched.hip", "blocktri_vbatched.hip")))
     say()
     rng = np.random.default_rng(31)
-    for (n, tmax, batch) in SHAPES:
+    for (n, tmax, batch) in SHAPES if "ragged" in sections else ():
         for kind in ("uniform", "log-uniform", "mostly short"):
             ragged_section(n, tmax, batch, kind, a.reps, rng)
-    for (n, T, batch) in EQUAL:
+    for (n, T, batch) in EQUAL if "equal" in sections else ():
         equal_section(n, T, batch, a.reps)
-    long_section(a.reps, rng)
+    if "long" in sections:
+        long_section(a.reps, rng)
+    if "parent" in sections and a.parent_lib:
+        libs = {"this": _lib.lib(), "parent": C.CDLL(a.parent_lib)}
+        for name in ENTRIES:
+            getattr(libs["parent"], name).restype, getattr(libs["parent"], name).argtypes = _lib.SIGNATURES[name]
+        held = [parent_section(n, T, batch, a.reps, libs) for (n, T, batch) in EQUAL]
+        say("every row within 1 + max(0.02, the parent's own spread) of the parent's time: %s" % ("yes" if all(held) else "NO"))
+        say()
+        resources()
+    elif "parent" in sections:
+        say("this build against the parent commit's: not measured (no --parent-lib given)")
     OUT[0].close()
 
 
